@@ -11,6 +11,12 @@ per GPU: gather -> 3 layers -> head -> BCE(sum) -> backward -> dense-semantics A
 rows (what the reference's dense `torch.optim.Adam` + `get_regularization_loss` do every step) -> Adam on the
 other parameters.  Dropout is on (p = 0.1, four sites per layer).  Inputs are synthetic, AliCCP-shaped
  and already resident in HBM when the timed region starts.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`metric`, `value`, `unit`, `ms_per_step`, ...).
+`--full` adds everything else this file measures or checks: per-phase and per-kernel times with the roofline of the dominant
+kernel, the gather probes, the evaluation forwards (fp32 and bf16), the logit parity against the CPU oracle, the sustained and
+fit() legs, the CPU baseline and the `other_configs` children.  `--dump-outputs DIR` writes what the last timed step computed
+(its predictions, the loss sum, the dense parameters and a fixed sample of table rows) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -273,13 +279,13 @@ OTHER_CONFIGS = (          # name, extra arguments, time limit in seconds
 
 
 def other_configs():
-    """`python bench.py <variant> --train-only --steps 20 --warmup 5` as a CHILD process per variant (started, never exec'ed; this
+    """`python bench.py <variant> --full --train-only --steps 20 --warmup 5` as a CHILD process per variant (started, never exec'ed; this
     process keeps its GPU context and waits), each line reduced to {metric, value, ms_per_step, roofline {kernel, bound, frac,
     launch_ms}, kernels ms per launch, gather (configs[4])}.  A variant that fails or overruns its limit is reported as such."""
     import subprocess
     res = {}
     for name, extra, limit in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "20", "--warmup", "5", "--train-only",
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "20", "--warmup", "5", "--full", "--train-only",
                "--no-other-configs"] + extra
         t0 = time.time()
         try:
@@ -304,6 +310,41 @@ def other_configs():
         except Exception as ex:                                                     # never take the headline line down
             res[name] = {"error": repr(ex)[:300]}
     return res
+
+
+# resident id batches of the timed loop: steps beyond this many cycle through them (as the sustained leg does), so that the
+# host-side synthesis - ~5 ms per batch - does not grow with --steps; every run of up to this many steps sees distinct batches
+MAX_RESIDENT_BATCHES = 256
+DUMP_ROWS_BYTES = 32 << 20      # --dump-outputs: table rows of the last batch, at most this many bytes
+DUMP_SAMPLE_ROWS = 65536        # --dump-outputs: seeded sample of the embedding arena's rows
+
+
+def dump_outputs(dirname, model, eng, Xb, prob):
+    """What the timed path computed in its last step, as DIR/<name>.npy (float32 / float64, ~30 MB for the headline config):
+    `prob` the step's predicted probabilities [B], `bce_sum` the summed sample losses of the run's steps, `param.<key>` every
+    state_dict entry outside the embedding tables, `emb_rows_last_batch` [n, F, D] the rows of every field's table that the
+    last batch's ids name (the rows its gradient updated), `emb_arena_sample` [DUMP_SAMPLE_ROWS, D] rows of the embedding
+    arena at fixed seeded positions (dense-semantics Adam + L2 moves every row every step).  Tables as they are after the
+    flush of the postponed row updates."""
+    os.makedirs(dirname, exist_ok=True)
+    F, D = len(CFG["fields"]), CFG["D"]
+    sd = model.state_dict()
+    out = {"bce_sum": eng.loss_sum.detach().cpu().numpy().astype(np.float64)}
+    if prob is not None:
+        out["prob"] = prob.detach().cpu().numpy().astype(np.float32)
+    for k, v in sd.items():
+        if not k.startswith(("embedding_dict.", "linear_model.embedding_dict.")):
+            out[f"param.{k}"] = v.detach().cpu().numpy().astype(np.float32)
+    n = min(Xb.shape[0], DUMP_ROWS_BYTES // (F * D * 4))
+    ids = Xb[:n, :F].long()
+    out["emb_rows_last_batch"] = torch.stack([sd[f"embedding_dict.{f}.weight"].index_select(0, ids[:, i].to(
+        sd[f"embedding_dict.{f}.weight"].device)) for i, f in enumerate(CFG["fields"])], 1).cpu().numpy().astype(np.float32)
+    arena = model.embedding_arena
+    pos = np.sort(np.random.RandomState(2024).randint(0, arena.shape[0], size=min(DUMP_SAMPLE_ROWS, arena.shape[0])))
+    out["emb_arena_sample"] = arena.detach()[torch.from_numpy(pos).to(arena.device)].cpu().numpy().astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    return sum(a.nbytes for a in out.values())
 
 
 def launch_ranks(n: int) -> int:
@@ -354,7 +395,15 @@ def main():
     ap.add_argument("--with-gather", action="store_true", help="with --train-only: also run the gather probes (the c5 line of other_configs)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the `other_configs` object (configs[3], gate, skewed ids, configs[4]: one child process each)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: phase / kernel times and roofline, gather probes, evaluation forwards (fp32, bf16), "
+                         "logit parity vs the CPU oracle, sustained and fit() legs, CPU baseline, other_configs (the options above "
+                         "that select or skip these act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     import satrans_amd  # noqa: F401  (before the first GPU call: its import sets the HIP runtime's stream-queue default)
     global CFG
     CFG = make_config(args.config, args.table_rows)
@@ -411,7 +460,7 @@ def main():
     B, K, W = args.batch, args.steps, args.warmup
     t_build = time.time()
     model = build_model("cpu", args.lr, args.flag)                                 # seeded init on CPU, as the reference
-    do_cpu = world == 1 and args.cpu_steps > 0 and not args.train_only
+    do_cpu = args.full and world == 1 and args.cpu_steps > 0 and not args.train_only
     # CPU leg of configs[4]: the oracle's dense step needs ~5 table-sized host buffers (parameters, gradient, two Adam moments,
     # regulariser graph) - 128 GB at 100 M rows.  Its bounded sample therefore runs the same step on 2 M-row tables (said so in
     # `cpu_baseline.sample`); its per-sample cost is dominated by the table sweeps, so this FLATTERS the CPU.
@@ -432,14 +481,13 @@ def main():
         print(f"[bench] model built in {time.time() - t_build:.1f}s; tables {model.embedding_arena.numel() * 4 / 1e6:.0f} MB",
               file=sys.stderr)
 
-    X, y = synth_batches((K + W) * B, seed=100 + rank, ids=args.ids)
+    n_res = min(K + W, MAX_RESIDENT_BATCHES)     # resident batches; a step names the batch that follows it, as `fit` does
+    X, y = synth_batches(n_res * B, seed=100 + rank, ids=args.ids)                 # (engine._prepare_async)
     Xd, yd = torch.from_numpy(X).to(device), torch.from_numpy(y).to(device)
     model.train()
 
-    n_res = K + W               # resident batches; a step names the batch that follows it, as `fit` does (engine._prepare_async)
-
     def step(i):
-        j = (i + 1) % n_res
+        i, j = i % n_res, (i + 1) % n_res
         eng.train_step(Xd[i * B:(i + 1) * B], yd[i * B:(i + 1) * B], next_X=Xd[j * B:(j + 1) * B])
 
     if world > 1 or force_exchange:
@@ -453,7 +501,8 @@ def main():
     eng.flush_lazy()
     # per-phase HIP events are recorded on every 4th step of the timed region: ~40 event records per step cost
     # ~0.4 ms/step (measured 2.13 vs 1.69 ms/step), which would distort the very number being reported
-    timers = {} if not args.no_phase_timing else None
+    # (--full only: a plain run times the steps alone)
+    timers = {} if (args.full and not args.no_phase_timing) else None
     if not bool(eng._ws.get(B, {}).get("generic")):
         eng.untimed_phases = frozenset(LAYER_PHASES)      # their durations come from the dispatches themselves (read_dispatch_ms)
     if world > 1:
@@ -481,6 +530,10 @@ def main():
     eng.timers = None
     eng.flush_lazy()          # (replica synchronisation of the owner form, outside the timed region and its phase timers)
     eng.timers = _t
+    if args.dump_outputs and rank == 0:
+        last = (W + K - 1) % n_res
+        nbytes = dump_outputs(args.dump_outputs, model, eng, Xd[last * B:(last + 1) * B], eng.last_prob())
+        print(f"[bench] outputs of the last timed step: {nbytes / 1e6:.1f} MB in {args.dump_outputs}", file=sys.stderr)
     per_rank_ms = [elapsed / K * 1e3]
     if world > 1:
         cdev = "cpu" if dist.get_backend() == "gloo" else device
@@ -501,6 +554,39 @@ def main():
             collectives[k] = {"calls_total": v["calls"], "bytes_sent_total": v["bytes_in"], "bytes_received_total": v["bytes_out"],
                               "note": "replica synchronisation at flush points, outside the timed region"}
     eng.raise_if_bad_ids()
+
+    F, D, L, U = len(CFG["fields"]), CFG["D"], CFG["L"], CFG["units"][0]
+    value = world * B * K / elapsed
+    head = {
+        "metric": ("training samples/sec (AliCCP-shaped, emb=32, 3L/4H, meta_mode=QK)" if args.config == "aliccp" else
+                   f"training samples/sec ({args.config}-shaped{' SCALED tables' if CFG.get('scaled') else ''}, emb={D}, {L}L/{CFG['H']}H, meta_mode=QK)") +
+                  ("" if args.flag == "sota" else f" flag={args.flag}"),
+        "value": round(value, 1), "unit": "samples/s", "n_gpus": world, "steps": K, "warmup": W,
+        "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "products": "f32: v_mfma_f32_16x16x4_f32 (bit for bit an fmaf chain)",
+        "config": {"workload": f"{CFG['label']}, {model.embedding_arena.shape[0]:,} table rows "
+                               f"({model.embedding_arena.numel() * 4 / 1e6:,.0f} MB fp32), {args.ids} ids, dropout on, "
+                               f"dense-Adam+L2 semantics over all rows",
+                   "batch_per_gpu": B, "global_batch": B * world, "embedding_dim": D, "layers": L, "heads": CFG["H"],
+                   "fields": F, "parallelism": f"dp{world}"},
+    }
+    tail = {"per_rank_ms_per_step": [round(v, 4) for v in per_rank_ms], "collectives": collectives}
+
+    def emit(line):
+        sys.stdout.flush()
+        os.write(real_stdout, (json.dumps(line) + "\n").encode())
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+    if not args.full:                     # a plain run: the headline line and nothing else
+        if rank == 0:
+            emit({**head, **tail})
+        elif dist.is_initialized():
+            dist.destroy_process_group()
+        return
+
     phases = eng.phase_ms() if eng.timers is not None else {}
     dispatch = read_dispatch_ms(eng.lib) if eng.timers is not None else {}
     eng.timers = None
@@ -599,7 +685,6 @@ def main():
         return
 
     # ---- roofline of the dominant kernel ----------------------------------------------------------------
-    F, D, L, U = len(CFG["fields"]), CFG["D"], CFG["L"], CFG["units"][0]
     total_rows = model.embedding_arena.shape[0]
     uniq = int(torch.unique(eng._ws[B]["rows"]).numel()) if B in eng._ws else 0
     # per layer launch: projections + output 4 F D^2, MetaNet of Q and K 4 F D U (U = 2 D: 12 F D^2 in all),
@@ -886,21 +971,8 @@ def main():
             and args.ids == "uniform":
         others = other_configs()
 
-    value = world * B * K / elapsed
-    out = {
-        "metric": ("training samples/sec (AliCCP-shaped, emb=32, 3L/4H, meta_mode=QK)" if args.config == "aliccp" else
-                   f"training samples/sec ({args.config}-shaped{' SCALED tables' if CFG.get('scaled') else ''}, emb={D}, {L}L/{CFG['H']}H, meta_mode=QK)") +
-                  ("" if args.flag == "sota" else f" flag={args.flag}"),
-        "value": round(value, 1), "unit": "samples/s", "n_gpus": world, "steps": K, "warmup": W,
-        "ms_per_step": round(elapsed / K * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "products": "f32: v_mfma_f32_16x16x4_f32 (bit for bit an fmaf chain)",
-        "config": {"workload": f"{CFG['label']}, {model.embedding_arena.shape[0]:,} table rows "
-                               f"({model.embedding_arena.numel() * 4 / 1e6:,.0f} MB fp32), {args.ids} ids, dropout on, "
-                               f"dense-Adam+L2 semantics over all rows",
-                   "batch_per_gpu": B, "global_batch": B * world, "embedding_dim": D, "layers": L, "heads": CFG["H"],
-                   "fields": F, "parallelism": f"dp{world}"},
+    emit({
+        **head,
         "fwd_logit_max_abs_err_vs_cpu_oracle": err,
         "fwd_logit": {"max_abs_err_vs_cpu_oracle": err, "training_forward_dropout_off_max_abs_err": err_train,
                       "max_abs_logit": logit_scale, "samples": 2048,
@@ -910,12 +982,8 @@ def main():
         "phase_sum_ms_per_step": round(phase_sum, 4), "phase_sum_frac_of_step": round(phase_sum / (elapsed / K * 1e3), 4),
         "roofline": roofline, "kernels": kernels, "kernels_serial": kernels_serial, "gather": gather,
         "forward_only": forward_only, "forward_only_bf16": forward_bf16, "cpu_baseline": cpu, "other_configs": others,
-        "per_rank_ms_per_step": [round(v, 4) for v in per_rank_ms], "collectives": collectives,
-    }
-    sys.stdout.flush()
-    os.write(real_stdout, (json.dumps(out) + "\n").encode())
-    if dist.is_initialized():
-        dist.destroy_process_group()
+        **tail,
+    })
 
 
 if __name__ == "__main__":

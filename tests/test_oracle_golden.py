@@ -31,6 +31,10 @@ def test_loss_and_grads_match_reference(name):
     c = Case(name)
     P, spec = c.tensors("param"), c.spec()
     bce, reg, grads = O.loss_and_grads(P, c.X, c.y, spec)
+    # the same gradients in fp64: how far fp32 rounding moves each one on this machine.  The BLAS kernels and the thread
+    # count decide the fp32 summation order, so the recorded vectors come back bit for bit only where they were recorded;
+    # the reference's fp32 result and this one are each about that far from the exact value
+    _, _, g64 = O.loss_and_grads(c.tensors("param", torch.float64), c.X.double(), c.y.double(), spec)
     z = c.z
     assert bce == pytest.approx(float(z["train/bce"]), rel=1e-6)
     assert reg == pytest.approx(float(z["train/reg"]), rel=1e-5)
@@ -38,10 +42,11 @@ def test_loss_and_grads_match_reference(name):
     assert set(want) <= set(grads), set(want) - set(grads)
     for k, g in want.items():
         scale = max(1e-6, float(np.abs(g).max()))
-        np.testing.assert_allclose(grads[k].numpy(), g, rtol=0, atol=2e-5 * scale, err_msg=k)
-    # keys the reference never gives a gradient stay without one
+        noise = float((grads[k].double() - g64[k]).abs().max())
+        np.testing.assert_allclose(grads[k].numpy(), g, rtol=0, atol=max(2e-5 * scale, 3.0 * noise), err_msg=k)
+    # keys the reference never gives a gradient stay without one: each is an alias of a key that has one
     for k in grads:
-        assert k in want or any(torch.equal(grads[k], torch.from_numpy(want[a])) for a in want if want[a].shape == grads[k].shape), k
+        assert k in want or any(torch.equal(grads[k], grads[a]) for a in want if grads[a].shape == grads[k].shape), k
 
 
 @pytest.mark.parametrize("name", ADAM_CASES)

@@ -30,15 +30,15 @@ bash tools/pmc_c5.sh > $o/pmc_c5.log 2>&1
 python tools/pmc_c5_summary.py gpurun_out/pmc_c5 6 > $o/c5_pmc_summary.json 2> $o/c5_pmc_summary.err
 rm -rf gpurun_out/pmc_c5
 cp $o/c5_pmc_summary.json profiles/r06_c5_pmc_summary.json
-( time python bench.py > $o/bench_default.json 2> $o/bench_default.err ) 2> $o/bench_default.time; echo "bench rc=$?"; tail -3 $o/bench_default.time
+( time python bench.py --full > $o/bench_default.json 2> $o/bench_default.err ) 2> $o/bench_default.time; echo "bench rc=$?"; tail -3 $o/bench_default.time
 rocprofv3 --kernel-trace --stats --output-format csv -d $o/ks5 -o p -- python3 bench.py --config c5 --train-only --steps 10 --warmup 2 --no-phase-timing > $o/ks5.log 2>&1
 python tools/kernel_stats.py $(find $o/ks5 -name "*kernel_stats.csv" | head -1) 45 > $o/c5_kernel_stats.md
 cp $(find $o/ks5 -name "*kernel_stats.csv" | head -1) $o/c5_kernel_stats.csv
 rm -rf $o/ks5
-python bench.py --flag sota-bilinear --train-only > $o/bench_bilinear.json 2>/dev/null
-SATRANS_FORCE_EXCHANGE=1 python bench.py --train-only > $o/bench_owner.json 2>/dev/null
-SATRANS_FORCE_EXCHANGE=1 SATRANS_OWNER_PREFETCH=1 python bench.py --train-only > $o/bench_owner_prefetch.json 2>/dev/null
-SATRANS_BENCH_SHARE_GPU=1 python bench.py --gpus 2 --train-only --steps 10 --warmup 3 > $o/bench_two_ranks_one_gpu_gloo.json 2> $o/bench_two_ranks.err; echo "two ranks rc=$?"
+python bench.py --full --flag sota-bilinear --train-only > $o/bench_bilinear.json 2>/dev/null
+SATRANS_FORCE_EXCHANGE=1 python bench.py --full --train-only > $o/bench_owner.json 2>/dev/null
+SATRANS_FORCE_EXCHANGE=1 SATRANS_OWNER_PREFETCH=1 python bench.py --full --train-only > $o/bench_owner_prefetch.json 2>/dev/null
+SATRANS_BENCH_SHARE_GPU=1 python bench.py --full --gpus 2 --train-only --steps 10 --warmup 3 > $o/bench_two_ranks_one_gpu_gloo.json 2> $o/bench_two_ranks.err; echo "two ranks rc=$?"
 python tools/fake_world.py 1 2 4 8 > $o/fake_world_owner.txt 2>/dev/null
 python tools/experiments/r06_fit_epoch.py > $o/fit_epoch.txt 2>/dev/null
 head -c 700 $o/bench_default.json

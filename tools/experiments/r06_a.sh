@@ -4,7 +4,7 @@ cd "$(dirname "$0")/../.." || exit 1
 o=gpurun_out/r06; mkdir -p $o
 tag=${1:-a}
 python -m pytest tests -m gpu -x -q > $o/pytest_$tag.log 2>&1; tail -5 $o/pytest_$tag.log
-python bench.py --train-only --steps 40 --warmup 10 > $o/bench_$tag.json 2> $o/bench_$tag.err
+python bench.py --full --train-only --steps 40 --warmup 10 > $o/bench_$tag.json 2> $o/bench_$tag.err
 python - <<P
 import json
 d = json.load(open("$o/bench_$tag.json"))

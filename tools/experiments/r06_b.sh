@@ -4,7 +4,7 @@ cd "$(dirname "$0")/../.." || exit 1
 o=gpurun_out/r06; mkdir -p $o
 tag=${1:-b}
 bash tools/experiments/r06_a.sh $tag
-python bench.py --train-only --steps 40 --warmup 10 --config alimama > $o/bench_${tag}_alimama.json 2> /dev/null
+python bench.py --full --train-only --steps 40 --warmup 10 --config alimama > $o/bench_${tag}_alimama.json 2> /dev/null
 python - <<P
 import json
 d = json.load(open("$o/bench_${tag}_alimama.json"))

@@ -5,7 +5,7 @@
 cd "$(dirname "$0")/../.." || exit 1
 for round in 1 2; do
   for lib in "" tools/experiments/_variants/lib_bf16_*.so; do
-    r=$(SATRANS_LIB_PATH=${lib:+$PWD/$lib} python bench.py --cpu-steps 0 --no-other-configs --sustained-steps 0 --fit-batches 0 --steps 5 --warmup 2 2>/dev/null | tail -1 | python -c "
+    r=$(SATRANS_LIB_PATH=${lib:+$PWD/$lib} python bench.py --full --cpu-steps 0 --no-other-configs --sustained-steps 0 --fit-batches 0 --steps 5 --warmup 2 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print(d['forward_only_bf16']['ms_per_batch'], d['forward_only']['ms_per_batch'])")
     echo "round $round ${lib:-shipped}: bf16 / fp32 forward ms per 32768: $r"

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/../.." || exit 1
 o=gpurun_out/r06; mkdir -p $o
 python -m pytest tests -m gpu -x -q > $o/pytest_e.log 2>&1; tail -3 $o/pytest_e.log
 python tools/experiments/r06_adam_drift.py > $o/adam_drift.txt 2> $o/adam_drift.err; cat $o/adam_drift.txt; tail -3 $o/adam_drift.err
-( time python bench.py > $o/bench_default.json 2> $o/bench_default.err ) 2>&1 | tail -3
+( time python bench.py --full > $o/bench_default.json 2> $o/bench_default.err ) 2>&1 | tail -3
 python - <<P
 import json
 d = json.load(open("$o/bench_default.json"))

@@ -9,7 +9,7 @@ SATRANS_LIB_PATH=$PWD/tools/experiments/_variants/lib_lane.so python tools/exper
 SATRANS_LIB_PATH=$PWD/tools/experiments/_variants/lib_lane.so python tools/experiments/r06_adam_noise.py fast
 } 2>/dev/null | tee $o/adam_noise.txt
 python -m pytest tests -m gpu -x -q > $o/pytest_f.log 2>&1; tail -3 $o/pytest_f.log
-python bench.py --no-other-configs --cpu-steps 0 --sustained-steps 0 --fit-batches 0 > $o/bench_fwd.json 2> $o/bench_fwd.err
+python bench.py --full --no-other-configs --cpu-steps 0 --sustained-steps 0 --fit-batches 0 > $o/bench_fwd.json 2> $o/bench_fwd.err
 python - <<P
 import json
 d = json.load(open("$o/bench_fwd.json"))
