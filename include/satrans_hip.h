@@ -31,7 +31,8 @@ extern "C" {
  *    was bumped one round late); round 4 added satrans_layer_bwd_head (a new entry point, no struct changed).  A caller built against an
  *    older header passes a shorter struct: satrans_abi_version() must be compared with this constant before any other call. */
 /* 6: satrans_adam_hparams gained the trailing `arith` field (round 6). */
-#define SATRANS_ABI_VERSION 6
+/* 7: the scenario attention statistics (satrans_attn_stats_workspace_bytes, satrans_attn_stats_accumulate); no struct changed. */
+#define SATRANS_ABI_VERSION 7
 
 /* error codes */
 #define SATRANS_OK 0
@@ -528,6 +529,22 @@ int satrans_embed_grad_dense(const float* arena, const int32_t* sorted_rows, con
 
 /* Sum of `count` doubles in index order -> out[0] (+= when accumulate != 0). */
 int satrans_sum_f64(const double* v, int64_t count, double* out, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Scenario-specific attention maps: predict's `showattn` branch (reference models/meta_basemodel.py:421-426, 439-458,
+ * 506-514), the per-(scenario, label class) sums of a layer's `normalized_att_scores` over the samples of a batch.
+ *   att   [H, B, F, F] one layer's attention in the caller's sample order, as satrans_layer_fwd / satrans_layer_fwd_generic
+ *         write it
+ *   key   [B] int32: the accumulator row of every sample, 3 j + c for scenario j and class c (0: label 1, 1: label 0, 2: any
+ *         other label), or -1 for a sample that counts nowhere (a key outside [-1, K) counts nowhere too)
+ *   acc   [K, H, F, F] fp64, K = 3 S, ACCUMULATED: acc[k] += the sum of att[:, b] over the samples b with key[b] == k
+ * Deterministic: no float atomics; a stable grouping of the samples by scenario, fixed blocks of 128 sample positions per
+ * scenario summed in fp64 (one sum per class), the block sums folded in a fixed order.  The partition depends on B, the scenario
+ * counts and the shape only, so two calls on the same inputs give the same bits.  Any F, odd F included.  workspace:
+ * satrans_attn_stats_workspace_bytes(B, H, F, K) bytes (-1 on bad sizes, K not a multiple of 3 included). */
+int64_t satrans_attn_stats_workspace_bytes(int B, int H, int F, int K);
+int satrans_attn_stats_accumulate(const float* att, const int32_t* key, int B, int H, int F, int K, double* acc,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
 
 /* The per-step training metrics of fit(verbose > 0) (meta_basemodel.py:330-337: sklearn log_loss and roc_auc_score on host
  * copies of every batch) for one batch in one launch: out[0] = log_loss(y, p.astype(float64)) (probabilities clipped to

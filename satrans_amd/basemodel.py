@@ -731,32 +731,99 @@ class BaseModel(nn.Module):
         return {"auc": auc, "domain_auc": per, "loss": loss, "pred": pred}
 
     def predict(self, x, batch_size=256, y=None, domain_ids=None):
-        """float64 [N,1] probabilities; models/meta_basemodel.py:401-517 (without the showattn/instattn
-        paper-figure branches)."""
+        """float64 [N,1] probabilities; models/meta_basemodel.py:401-517 (without the instattn paper-figure branch).
+
+        With 'showattn' in the flag (reference :421-426, 439-458, 506-514) the call also leaves the scenario-specific attention
+        maps on the model: `attn_list_pos` / `attn_list_neg` / `attn_list_all`, lists [L][S] of float32 numpy [H, F, F] (S =
+        num_domains_list[0]), the mean `normalized_att_scores` of the samples of scenario j (domain id j + bias, bias = 1 when
+        min(domain_ids) == 1) with y == 1 / y == 0 / any label, and `inst_attn_dict = []`; see attention_statistics().  `y` is
+        required there; `domain_ids` defaults to the model's first scenario column of `x`.  Deviation from the reference: an
+        empty (scenario, class) pair gives an all-NaN map where the reference crashes."""
+        if self.flag and 'showattn' in self.flag:
+            pred, st = self._attention_pass(x, y, domain_ids, batch_size)
+            mean = st["mean"].astype(np.float32)
+            L, S = mean.shape[0], mean.shape[1]
+            self.attn_list_pos = [[mean[i, j, 0] for j in range(S)] for i in range(L)]
+            self.attn_list_neg = [[mean[i, j, 1] for j in range(S)] for i in range(L)]
+            self.attn_list_all = [[mean[i, j, 2] for j in range(S)] for i in range(L)]
+            self.inst_attn_dict = []                # (the reference's `break` at meta_basemodel.py:442 keeps it empty)
+            return pred
+        return self._predict_pass(x, batch_size)
+
+    def attention_statistics(self, x, y, domain_ids=None, batch_size=256) -> dict:
+        """The per-scenario attention maps of predict's 'showattn' branch, independent of the flag:
+        {"sum": float64 [L, S, 3, H, F, F], "count": int64 [S, 3], "mean": float64 sum / count (NaN where the count is 0),
+        "bias": int}, class order (pos: y == 1, neg: y == 0, all).  Scenario j is domain id j + bias (bias = 1 when
+        min(domain_ids) == 1 over the whole array, else 0; ids naming no scenario count nowhere; a label that is neither 0 nor 1
+        counts in `all` only); `domain_ids` defaults to the model's first scenario column of `x`.  The sums are taken on the
+        device batch by batch (csrc/attn_stats.hip), deterministic for a given batch_size; the evaluation runs on the fp32
+        layer kernels whatever set_forward_precision chose.  Sums and counts are additive across shards of the data."""
+        return self._attention_pass(x, y, domain_ids, batch_size)[1]
+
+    def _attention_pass(self, x, y, domain_ids, batch_size):
+        from . import attn_stats as AS
+        if y is None:
+            raise ValueError("attention statistics need the labels: pass y")
+        if domain_ids is None:
+            domain_ids = self._column_values(x, self.domain_column_list[0])
+        S = int(self.num_domains_list[0])
+        bias = AS.scenario_bias(domain_ids)
+        keys = AS.class_keys(domain_ids, y, S, bias)
+        engine = self._require_engine()
+        ctx = AS.AttentionStatistics(engine, S)
+        pred = self._predict_pass(x, batch_size, ctx, keys)
+        return pred, AS.finish(ctx.raw_sum(), keys, S, bias)
+
+    def _column_values(self, x, name) -> np.ndarray:
+        """The values of feature `name` (its first column) out of a dict / list of per-feature arrays / packed matrix."""
+        lo = self.feature_index[name][0]
+        if isinstance(x, dict):
+            v = np.asarray(x[name])
+            return v.reshape(v.shape[0], -1)[:, 0]
+        if isinstance(x, np.ndarray) and x.ndim == 2:
+            return x[:, lo]
+        at = 0
+        for c in self._columns(x):
+            if lo < at + c.shape[1]:
+                return c[:, lo - at]
+            at += c.shape[1]
+        raise ValueError(f"x has no column for feature {name}")
+
+    def _predict_pass(self, x, batch_size, stats=None, keys=None):
         engine = self._require_engine()
         was_training = self.training
         self.eval()
         is_matrix = isinstance(x, np.ndarray) and x.ndim == 2 and not isinstance(x, (dict, list))
         cols = [x] if is_matrix else self._columns(x)
         n_rows, n_cols = cols[0].shape[0], sum(c.shape[1] for c in cols)
+        if keys is not None and len(keys) != n_rows:
+            raise ValueError(f"x has {n_rows} rows, the labels / domain ids {len(keys)}")
         import os as _os
         stream = getattr(self, "stream_input", None)
         if stream is None:
             stream = _os.environ.get("SATRANS_STREAM_INPUT", "0") == "1" or n_rows * n_cols * 4 > (8 << 30)
         out = torch.empty((n_rows, 1), dtype=torch.float32, device=self.device)
+        keys_d = torch.from_numpy(keys).to(self.device) if stats is not None else None
+
+        def run(xb, lo, hi):
+            if stats is None:
+                return engine.forward(xb, training=False)
+            stats.set_batch(keys_d[lo:hi])
+            return engine.forward(xb, training=False, stats=stats)
+
         if stream:                                      # host-resident, double-buffered (satrans_amd/pipeline.py)
             from .pipeline import HostBatchFeeder
             packed = x if is_matrix else self._pack(x)
             host_ids, host_dense = self._host_matrices(packed)
             lo = 0
             for xb, _ in HostBatchFeeder(host_ids, None, batch_size, self.device, None, host_dense):
-                out[lo:lo + len(xb)] = engine.forward(xb, training=False)
+                out[lo:lo + len(xb)] = run(xb, lo, lo + len(xb))
                 lo += len(xb)
         else:
             data = self._to_device_matrix(x) if is_matrix else self._device_matrix_from_columns(cols)
             for lo in range(0, data.shape[0], batch_size):
                 hi = min(data.shape[0], lo + batch_size)
-                out[lo:hi] = engine.forward(data[lo:hi], training=False)
+                out[lo:hi] = run(data[lo:hi], lo, hi)
         engine.raise_if_bad_ids()
         if was_training:
             self.train()
