@@ -11,7 +11,8 @@ loss, append the result line the reference appends to `<data>_results.csv`, opti
 Differences from the reference script: the two import lines, the HDF5 columns come through
 satrans_amd.pipeline.load_h5_columns (no h5py needed, memory-mapped), and the evaluation report is one call
 (`evaluate_domains`: the same numbers as main.py:353-374, computed on the device).  `--data_max` overrides the reference's
-hard-coded column maxima (main.py:124-127) for other datasets with the same layout."""
+hard-coded column maxima (main.py:124-128) for other datasets with the same layout.  `--history_topk k` switches on the
+four multi-valued history columns (main.py:102, data from aliccp_dataset_processing.py's generate_topk_history_features)."""
 import argparse
 import json
 import os
@@ -23,14 +24,16 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from satrans_amd import SATrans, SparseFeat, get_feature_names  # noqa: E402
+from satrans_amd import SATrans, SparseFeat, VarLenSparseFeat, get_feature_names  # noqa: E402
 from satrans_amd.pipeline import load_h5_columns  # noqa: E402
 
 SPARSE = ['101', '121', '122', '124', '125', '126', '127', '128', '129', '205', '206', '207', '210', '216', '508', '509', '702',
           '853', '301']                                                             # main.py:99-101
 DATA_MAX = {'101': 444861, '121': 97, '122': 13, '124': 2, '125': 7, '126': 3, '127': 3, '128': 2, '129': 4, '205': 4348615,
             '206': 8993, '207': 695124, '210': 99606, '216': 234880, '508': 8185, '509': 472354, '702': 167813, '853': 91358,
-            '301': 3}                                                               # main.py:124-127
+            '301': 3,
+            '10914': 12521, '11014': 2981269, '15014': 99553, '12714': 426099}      # main.py:124-128
+HISTORY = ['10914', '11014', '15014', '12714']                                      # main.py:102 (top-k history lists)
 
 
 def main(argv=None):
@@ -49,6 +52,9 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=1)
     ap.add_argument("--data_max", default=None, help="JSON {column: max id} instead of the reference's AliCCP maxima")
     ap.add_argument("--results", default=None, help="CSV to append the reference's result line to (default: none)")
+    ap.add_argument("--history_topk", type=int, default=0,
+                    help="k > 0: add the four top-k history columns as VarLenSparseFeat(maxlen=k, combiner='max'), read from "
+                         "'<col>_<k>' (the reference's commented-out switch, main.py:102,185-188)")
     ap.add_argument("--dump", default=None, help="path for torch.save(model.cpu().state_dict()) (reference flag 'dump')")
     args = ap.parse_args(argv)
 
@@ -60,9 +66,14 @@ def main(argv=None):
         dist.init_process_group("nccl", device_id=torch.device(f"cuda:{local}"))
     device = f"cuda:{local}"
     data_max = dict(DATA_MAX, **(json.loads(args.data_max) if args.data_max else {}))
-    cols = ['click'] + SPARSE
+    k = args.history_topk
+    hist = [f"{c}_{k}" for c in HISTORY] if k > 0 else []
+    cols = ['click'] + SPARSE + hist
     train = dict(load_h5_columns(args.h5, 'ctr_train' + args.postfix, cols))       # main.py:106-109 (get_aliccp_ctr_df)
     test = dict(load_h5_columns(args.h5, 'ctr_test' + args.postfix, cols))
+    for d in (train, test):                                                         # [N, k] int32 lists, padded with id 0
+        for c in HISTORY if k > 0 else []:
+            d[c] = d.pop(f"{c}_{k}")
     if int(np.min(train['301'])) == 0:                                              # scenario ids start at 1 (main.py:112-114)
         train['301'] = np.asarray(train['301']) + 1
         test['301'] = np.asarray(test['301']) + 1
@@ -72,6 +83,8 @@ def main(argv=None):
     domain_cols = [args.domain_col]
     num_domains_list = [max(len(np.unique(train[c])), data_max[c]) for c in domain_cols]          # main.py:131-132
     columns = [SparseFeat(f, vocabulary_size=int(data_max[f]) + 2, embedding_dim=args.embedding_dim) for f in SPARSE]
+    columns += [VarLenSparseFeat(SparseFeat(c, vocabulary_size=int(data_max[c]) + 2, embedding_dim=args.embedding_dim), maxlen=k,
+                                 combiner='max') for c in (HISTORY if k > 0 else [])]             # main.py:185-188
     names = get_feature_names(columns)
     model = SATrans(columns, columns, domain_cols, num_domains_list, att_layer_num=0, domain_att_layer_num=args.att_layer_num,
                     att_head_num=args.att_head_num, use_linear=False, use_dnn=False, meta_mode=args.meta_mode, seed=args.seed,

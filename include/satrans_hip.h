@@ -32,6 +32,9 @@ extern "C" {
  *    older header passes a shorter struct: satrans_abi_version() must be compared with this constant before any other call. */
 /* 6: satrans_adam_hparams gained the trailing `arith` field (round 6). */
 /* 7: the scenario attention statistics (satrans_attn_stats_workspace_bytes, satrans_attn_stats_accumulate); no struct changed. */
+/*    Also in 7, added later: the pooled gather of VarLenSparseFeat fields and its backward (satrans_pool_field,
+ *    satrans_pool_gather_fwd, satrans_pool_bwd, satrans_pool_argmax_bytes).  Purely additive - no existing struct or entry point
+ *    changed - so a caller built against the earlier version-7 header runs unchanged; the binding checks the new symbols at load. */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -108,6 +111,51 @@ int satrans_bucket_scenarios(const void* X, int id_dtype, int64_t x_stride, int 
 int satrans_gather_fwd(const float* arena, const int64_t* row_span, const int32_t* cols, const void* X,
                        int id_dtype, int64_t x_stride, int B, int F, int D, float* out,
                        int32_t* rows_out, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pooled gather for models with VarLenSparseFeat fields: deepctr-torch's varlen_embedding_lookup + SequencePoolingLayer
+ * behind the SparseFeat lookups, concatenated (reference meta_basemodel.py:519-545).  Field f occupies the `maxlen` SLOTS
+ * [slot, slot + maxlen) of a sample; R = sum of maxlen over the fields (a SparseFeat is one slot with combiner COPY).
+ *   fields     [F] HOST array, sparse fields first, then the varlen ones (F <= SATRANS_POOL_MAX_FIELDS; checked here and
+ *              passed to the kernel by value).  slot / varlen must number the fields consecutively from 0.
+ *   ids        X[b, col + s] (`.long()` truncation of fp32 ids); mask = s < X[b, len_col] when len_col >= 0, else id != 0
+ *   SUM        sum over the valid slots in slot order (fp32)
+ *   MEAN       the same sum / (count + 1e-8f), a true division; an empty list gives 0
+ *   MAX        per element max over slots of (E - (1 - mask) * 1e9f); the first maximal slot wins.  An all-padding list
+ *              gives about -1e9 (the reference's value)
+ *   arena      [arena_rows, D]; an id outside [0, hi - lo) - padding slots included - sets bit 0 of *status, reads as zeros and
+ *              is recorded as row lo
+ *   src, src_rows  optional: the row of slot (b, r) is read from src + src_rows[b * R + r] * D instead of the arena (rows that
+ *              arrived from their owners); rows_out is still computed from the ids
+ *   out        [B, F, D] pooled layer input, or NULL (rows-only mode)
+ *   rows_out   optional [B, R] int32 arena rows of every slot
+ *   mask_out   [B, Fv] uint32: bit s = slot s of varlen field v is valid (needed with out when Fv > 0)
+ *   argmax_out [B, Fv, D] uint8 (satrans_pool_argmax_bytes): slot of each MAX element (needed with out when Fv > 0)
+ * Backward: dx [B, F, D] -> gemb [B * R, D], row b * R + r = gradient of slot r's row: COPY dx; SUM dx at valid slots, 0 at
+ * padding; MEAN dx / (count + 1e-8f) at valid slots; MAX dx at the argmax slot of each element, 0 elsewhere.  Every element is
+ * written exactly once (no atomics). */
+#define SATRANS_POOL_COPY 0
+#define SATRANS_POOL_SUM 1
+#define SATRANS_POOL_MEAN 2
+#define SATRANS_POOL_MAX 3
+#define SATRANS_POOL_MAX_LEN 32
+#define SATRANS_POOL_MAX_FIELDS 64
+typedef struct satrans_pool_field {
+    int32_t col;      /* first X column */
+    int32_t maxlen;   /* 1 for a SparseFeat */
+    int32_t combiner; /* SATRANS_POOL_* */
+    int32_t len_col;  /* X column of the list length (length_name), or -1: mask = id != 0 */
+    int32_t slot;     /* first slot in [0, R) */
+    int32_t varlen;   /* index among the varlen fields, -1 for a SparseFeat */
+    int64_t lo, hi;   /* arena rows [lo, hi) of the field's table */
+} satrans_pool_field;
+int64_t satrans_pool_argmax_bytes(int B, int Fv, int D);
+int satrans_pool_gather_fwd(const float* arena, int64_t arena_rows, const float* src, const int32_t* src_rows,
+                            const satrans_pool_field* fields, int F, int R, int Fv, const void* X, int id_dtype,
+                            int64_t x_stride, int B, int D, float* out, int32_t* rows_out, uint32_t* mask_out,
+                            uint8_t* argmax_out, int32_t* status, void* stream);
+int satrans_pool_bwd(const float* dx, const satrans_pool_field* fields, int F, int R, int Fv, int B, int D,
+                     const uint32_t* mask, const uint8_t* argmax, float* gemb, void* stream);
 
 /* Measurement aid (bench.py): the READ side of the gather alone - arena rows by row number (the `rows_out` of
  * satrans_gather_fwd), eight rows in flight per thread, nothing written but a checksum per thread into `sink`

@@ -137,9 +137,9 @@ class BaseModel(nn.Module):
         return OrderedDict()
 
     def _table_order(self) -> List[str]:
-        sparse, _, _ = split_columns(self.dnn_feature_columns)
+        sparse, _, varlen = split_columns(self.dnn_feature_columns)
         names, seen = [], set()
-        for col in sparse:
+        for col in sparse + varlen:
             if col.embedding_name not in seen:
                 seen.add(col.embedding_name)
                 names.append(col.embedding_name)
@@ -390,8 +390,8 @@ class BaseModel(nn.Module):
         concatenate / cast passes over the whole dataset (the reference builds that matrix on the host:
         meta_basemodel.py:257-264).  Vocabularies of 2**24 and above keep the host path (`_host_matrices`: int64 ids + dense
         block)."""
-        sparse, _, _ = split_columns(self.dnn_feature_columns)
-        if max(c.vocabulary_size for c in sparse) >= (1 << 24):
+        sparse, _, varlen = split_columns(self.dnn_feature_columns)
+        if max(c.vocabulary_size for c in sparse + varlen) >= (1 << 24):
             return self._to_device_matrix(np.concatenate([c[lo:hi] for c in cols], axis=-1))
         n = (cols[0].shape[0] if hi is None else hi) - lo
         data = torch.empty(n, sum(c.shape[1] for c in cols), dtype=torch.float32, device=self.device)
@@ -423,8 +423,8 @@ class BaseModel(nn.Module):
     def _host_matrices(self, packed: np.ndarray):
         """-> (ids matrix, dense block or None) on the host: fp32 in the reference's layout while every vocabulary is below
         2**24, else int64 ids plus - when the model has DenseFeat columns - their float block (inputs.PackedInput)."""
-        sparse, dense, _ = split_columns(self.dnn_feature_columns)
-        if max(c.vocabulary_size for c in sparse) >= (1 << 24):
+        sparse, dense, varlen = split_columns(self.dnn_feature_columns)
+        if max(c.vocabulary_size for c in sparse + varlen) >= (1 << 24):
             if not np.issubdtype(packed.dtype, np.integer) and packed.dtype == np.float32 and np.abs(packed).max() >= (1 << 24):
                 raise ValueError("ids of 2**24 and above arrived as float32: they are already rounded; pass integers")
             block = None

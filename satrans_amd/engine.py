@@ -41,8 +41,11 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
         self.dev = m.embedding_arena.device
         N.require_gpu(m.embedding_arena, "SATrans")
         flag = m.flag
-        sparse, dense, _ = split_columns(m.dnn_feature_columns)
-        self.F = len(sparse)
+        sparse, dense, varlen = split_columns(m.dnn_feature_columns)
+        # layer fields: the SparseFeat ones, then the pooled VarLenSparseFeat ones (meta_basemodel.py:519-545)
+        self.F = len(sparse) + len(varlen)
+        self.varlen = list(varlen)
+        self.Fv = len(varlen)
         self.D = m.embedding_size
         self.H = m.att_head_num
         self.L = m.domain_att_layer_num
@@ -132,21 +135,40 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
                                             device=self.dev)
         self.n_cols = max(e for _, e in fi.values())
         # arena rows [lo, hi) of every FIELD's table (fields sharing an embedding_name share a table)
-        spans = [(m._table_rows[c.embedding_name][0], m._table_rows[c.embedding_name][0] + m._table_rows[c.embedding_name][1])
-                 for c in sparse]
+        def span(c):
+            lo, rows = m._table_rows[c.embedding_name]
+            return (lo, lo + rows)
+        spans = [span(c) for c in sparse]
         self.total_rows = m.embedding_arena.shape[0]
         self.row_span = torch.tensor(spans, dtype=torch.int64, device=self.dev).contiguous()
+        # row SLOTS of a sample: one per SparseFeat, `maxlen` per VarLenSparseFeat (padding slots included: they read row `lo`
+        # of their table and carry a zero gradient).  Without varlen fields R == F and a slot is a field.
+        slot_spans = spans + [span(c) for c in varlen for _ in range(c.maxlen)]
+        self.R = len(slot_spans)
         # optimizer classes (basemodel._rebind_storage puts the small tables first in the arena): arena row < small_rows
-        # <=> small table.  Every sample contributes exactly one row per field, so after sorting a batch's rows the first
-        # B * F_small positions are the small-table ones.
+        # <=> small table.  Every sample contributes exactly one row per slot, so after sorting a batch's rows the first
+        # B * F_small positions are the small-table ones (F_small counts slots).
         self.small_rows = int(m._arena_small_rows)
-        self.F_small = sum(1 for lo, _ in spans if lo < self.small_rows)
+        self.F_small = sum(1 for lo, _ in slot_spans if lo < self.small_rows)
+        self._pool_fields = None
+        if varlen:
+            # the pooled gather's field table (csrc/pool.hip): sparse fields copy their row, varlen fields pool `maxlen` slots
+            comb = {"sum": N.POOL_SUM, "mean": N.POOL_MEAN, "max": N.POOL_MAX}
+            descs, slot = [], 0
+            for c in sparse:
+                descs.append((fi[c.name][0], 1, N.POOL_COPY, -1, slot, -1) + span(c))
+                slot += 1
+            for v, c in enumerate(varlen):
+                len_col = fi[c.length_name][0] if c.length_name is not None else -1
+                descs.append((fi[c.name][0], c.maxlen, comb[c.combiner], len_col, slot, v) + span(c))
+                slot += c.maxlen
+            self._pool_fields = (N.PoolField * len(descs))(*[N.PoolField(*d_) for d_ in descs])
         # one-launch sort of a batch's rows, one workgroup per field (csrc/embed_adam.hip: satrans_embed_sort_fields): possible when
         # every field has a table of its own; the fields in arena order with the first row and the row count of their tables
         by_lo = sorted(range(len(spans)), key=lambda f: spans[f][0])
         own = all(spans[by_lo[k]][0] >= spans[by_lo[k - 1]][1] for k in range(1, len(by_lo))) and len(spans) <= 64
         self._sort_fields = None
-        if own and os.environ.get("SATRANS_SORT_FIELDS", "1") != "0":
+        if own and not varlen and os.environ.get("SATRANS_SORT_FIELDS", "1") != "0":
             Arr = C.c_int32 * len(spans)
             self._sort_fields = (Arr(*by_lo), Arr(*[spans[f][0] for f in by_lo]), Arr(*[spans[f][1] - spans[f][0] for f in by_lo]))
 
@@ -202,7 +224,8 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
         # The step's structure.  These are attributes, not environment switches: the shipped values are the ones below; the
         # parity tests flip them to hold the fused forms against the plain ones bit for bit.
         # the first layer reads its tokens straight from the embedding arena (no [B,F,D] gather output)
-        self.fuse_gather = True
+        # (models with VarLenSparseFeat fields: the pooled gather writes [B,F,D] - there is no row to read per field)
+        self.fuse_gather = not self.varlen
         # the last layer of a training step as one launch with the head fused in (satrans_layer_bwd_head): no forward launch
         # for that layer, no head launches, no [B,F,D] round trip of its output and gradient
         self.fuse_head = True
@@ -301,9 +324,13 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
             sid=torch.empty(B, **i32), order=torch.empty(B, **i32), seg=torch.empty(self.S + 1, **i32),
             bucket=torch.empty(int(self.lib.satrans_bucket_workspace_bytes(B, self.S)), dtype=torch.uint8, device=dev),
             acts=[torch.empty(B, F, D, **f32) for _ in range(self.L + 1)],
-            rows=torch.empty(B, F, **i32),
+            rows=torch.empty(B, self.R, **i32),
             prob=torch.empty(B, **f32), logit=torch.empty(B, **f32),
         )
+        if self.varlen:        # the pooled gather's valid-slot masks and max-argmax, read by its backward
+            ws["vmask"] = torch.empty(B, self.Fv, **i32)
+            ws["argmax"] = torch.empty(max(1, int(self.lib.satrans_pool_argmax_bytes(B, self.Fv, D))), dtype=torch.uint8,
+                                       device=dev)
         self._ws[B] = ws
         # Which layer kernels serve this shape: the fused / LDS-resident ones behind satrans_layer_fwd/_bwd, or - shapes
         # they cannot hold, e.g. 64 fields x embedding_dim 64 x MetaNet hidden 128 - the general path (csrc/layer_generic.hip),
@@ -331,7 +358,7 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
         f32 = dict(dtype=torch.float32, device=dev)
         i32 = dict(dtype=torch.int32, device=dev)
         f64 = dict(dtype=torch.float64, device=dev)
-        n_loc = B * F
+        n_loc = B * self.R
         n_s = B * self.F_small                       # sorted positions [0, n_s): small tables; [n_s, n_loc): large tables
         n_big = (n_loc - n_s) * world                # large-table positions of ALL ranks
         n_max = max(n_loc, n_big)
@@ -356,6 +383,8 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
                 ws["attn_save_floats"] = int(lib.satrans_layer_attn_save_floats(C.byref(desc)))
                 ws["attn_save"] = [None] * self.L
             ws["sorted_rows"] = torch.empty(n_loc, **i32)       # this rank's rows, sorted, and their source positions
+            if self.varlen:                                     # the gradient of every slot's row (satrans_pool_bwd)
+                ws["gslot"] = torch.empty(n_loc, D, **f32)
             ws["src"] = torch.empty(n_loc, **i32)
             ws["touched"] = torch.empty((self.total_rows + 31) // 32, **i32)
             ws["reg_unused"] = torch.zeros(int(lib.satrans_embed_reg_partials(self.total_rows, max(n_s, 1), D)), **f64)
@@ -551,7 +580,10 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
         ws["acts0_of"] = None if fuse else X
         ws["acts_sorted"] = bool(sorted_io)
         ws["acts_stacked"] = False
-        if not (fuse and rows_ready):
+        if self.varlen:
+            with self.phase("gather_fwd"):
+                self._pool_gather(X, ws, ws["acts"][0])
+        elif not (fuse and rows_ready):
             with self.phase("gather_fwd"):
                 N.check(lib.satrans_gather_fwd(self.m.embedding_arena.data_ptr(), self.row_span.data_ptr(),
                                                self.cols.data_ptr(), X.data_ptr(), idt, X.stride(0), B, self.F, self.D,
@@ -594,6 +626,23 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
             if stats is not None:
                 with self.phase("attn_stats"):
                     stats.accumulate(l, att_t, B, st)
+
+    def _pool_gather(self, X, ws, out) -> None:
+        """Varlen models: ids -> slot rows [B, R] and - `out` given - the pooled layer input [B, F, D] (csrc/pool.hip)."""
+        arena = self.m.embedding_arena
+        N.check(self.lib.satrans_pool_gather_fwd(
+            arena.data_ptr(), arena.shape[0], None, None, self._pool_fields, self.F, self.R, self.Fv, X.data_ptr(),
+            N.id_dtype_of(X), X.stride(0), X.shape[0], self.D, N.ptr(out), ws["rows"].data_ptr(),
+            ws["vmask"].data_ptr() if out is not None else None, ws["argmax"].data_ptr() if out is not None else None,
+            self.status.data_ptr(), self._stream()), "satrans_pool_gather_fwd")
+
+    def _pool_backward(self, dx, ws, B):
+        """Varlen models: layer 0's dx [B, F, D] -> the gradient of every slot's row [B * R, D] (csrc/pool.hip)."""
+        with self.phase("pool_bwd"):
+            N.check(self.lib.satrans_pool_bwd(dx.data_ptr(), self._pool_fields, self.F, self.R, self.Fv, B, self.D,
+                                              ws["vmask"].data_ptr(), ws["argmax"].data_ptr(), ws["gslot"].data_ptr(),
+                                              self._stream()), "satrans_pool_bwd")
+        return ws["gslot"]
 
     def after_step(self, fn, *tensors) -> None:
         """Launches that only READ what the step just produced - the probabilities of `last_prob()`, the labels: `fit`'s per-step
@@ -1006,6 +1055,8 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
                 after_layers(early_ev)
                 after_layers, early_ev = None, None
             cur = 1 - cur
+        # (layer 0's dx is in the caller's sample order on every path: only interior layers hand sorted activations on)
+        gemb = self._pool_backward(ws["dact"][cur], ws, B) if self.varlen else ws["dact"][cur]
 
         def finish():
             # what only the dense-parameter step needs: the slab reduction and the scenario-table backward
@@ -1057,7 +1108,7 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
                 g_clear.zero_()
             finish()
         self._last_prob = ws["prob"]
-        return ws["dact"][cur]
+        return gemb
 
     # ------------------------------------------------------------------------------------------------
     # next-batch preprocessing on a side stream
@@ -1174,6 +1225,9 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
         y = y.reshape(-1).to(torch.float32).contiguous()
         B = X.shape[0]
         self._ensure_train_state()
+        if self.varlen and parallel.exchange_enabled():
+            raise NotImplementedError("data-parallel training (row-ownership and replicated forms) of a model with "
+                                      "VarLenSparseFeat columns: train on one rank (DESIGN.md 7)")
         cfg = self.m._refresh_adam_cfg()              # lr schedulers / edited param_groups take effect at this step
         if cfg.get("kind", "adam") != "adam":
             return self._train_step_dense(X, y, cfg)
@@ -1194,7 +1248,7 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
         field f's table) - the only input the one-workgroup-per-field kernel may see; the rank-major concatenation of an
         exchange is not one."""
         lib = self.lib
-        if per_field and self._sort_fields is not None and touched is None and n == B * self.F and B <= 8192:
+        if per_field and self._sort_fields is not None and touched is None and n == B * self.R and B <= 8192:
             f_, lo_, n_ = self._sort_fields       # one workgroup per field, one launch
             N.check(lib.satrans_embed_sort_fields(rows.data_ptr(), B, self.F, f_, lo_, n_, out_rows.data_ptr(),
                                                   out_src.data_ptr(), self._stream()), "satrans_embed_sort_fields")
@@ -1228,11 +1282,14 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
                                                            ws["sorted_rows"].data_ptr(), ws["src"].data_ptr(),
                                                            self.status.data_ptr(), st), "satrans_embed_rows_sort_fields")
         else:
-            N.check(lib.satrans_gather_fwd(m.embedding_arena.data_ptr(), self.row_span.data_ptr(), self.cols.data_ptr(), X.data_ptr(),
-                                           N.id_dtype_of(X), X.stride(0), B, self.F, self.D, None, ws["rows"].data_ptr(),
-                                           self.status.data_ptr(), st), "satrans_gather_fwd(rows)")
+            if self.varlen:
+                self._pool_gather(X, ws, None)          # (rows only)
+            else:
+                N.check(lib.satrans_gather_fwd(m.embedding_arena.data_ptr(), self.row_span.data_ptr(), self.cols.data_ptr(),
+                                               X.data_ptr(), N.id_dtype_of(X), X.stride(0), B, self.F, self.D, None,
+                                               ws["rows"].data_ptr(), self.status.data_ptr(), st), "satrans_gather_fwd(rows)")
             with self.phase("embed_sort"):
-                self._sort_rows(ws, B, ws["rows"], B * self.F, ws["sorted_rows"], ws["src"], None, per_field=True)
+                self._sort_rows(ws, B, ws["rows"], B * self.R, ws["sorted_rows"], ws["src"], None, per_field=True)
 
     def _small_tables_step(self, ws, small_rows, h_emb, st):
         """Dense step over every row of the small tables (their gradient is the dense buffer g_small)."""
@@ -1262,7 +1319,7 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
         if l2 > 0:                                    # the step's regulariser term of the logged loss (pre-update weights)
             self.reg_sum += l2 * torch.sum(torch.square(m.embedding_arena.double()))
         gemb = self.backward(X, y, ws)
-        n_rows = B * self.F
+        n_rows = B * self.R
         rows_t, grads_t = ws["rows"], gemb
         if exch:
             # several ranks (reference semantics as for Adam: per-GPU batches, summed loss): the dense parameters' gradient is
@@ -1483,7 +1540,7 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
         y = y.reshape(-1).to(torch.float32).contiguous()
         B = X.shape[0]
         self._ensure_train_state()
-        n_rows = B * self.F
+        n_rows = B * self.R
         ws = self.train_workspace(B, 1)
         lib, st, m, D = self.lib, self._stream(), self.m, self.D
         self.loss_sum.zero_()

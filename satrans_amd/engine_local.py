@@ -24,7 +24,7 @@ class LocalStepMixin:
         # table classes only pay off when there is an exchange to shrink (one rank: +5 launches for nothing; tests force them)
         split = self.force_split
         small_rows = self.small_rows if split else 0
-        n_loc = B * self.F
+        n_loc = B * self.R
         n_s = B * self.F_small if split else 0
         n_b = n_loc - n_s
         l2 = m.l2_reg_embedding

@@ -56,7 +56,8 @@ class OwnerStepMixin:
     def plans_owner_counts(self) -> bool:
         """Whether plan_owner_counts would plan anything (fit() only waits for the whole sample order when it does)."""
         from . import parallel
-        return bool(parallel.exchange_enabled() and self.dp_mode == "owner" and self.lazy and self.F_small < self.F)
+        return bool(parallel.exchange_enabled() and self.dp_mode == "owner" and self.lazy and self.F_small < self.F
+                    and not self.varlen)
 
     def plan_owner_counts(self, ids: torch.Tensor, order: Optional[torch.Tensor], batch_size: int) -> None:
         """Owner form, optional: the per-step all-to-all split sizes of a whole epoch in ONE pass and ONE read-back, for callers

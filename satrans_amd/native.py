@@ -76,6 +76,17 @@ class MetaNetDesc(C.Structure):
                 ("tab_stride", C.c_int64), ("x", _vp), ("order", _vp), ("seg", _vp), ("tab", _vp), ("ln_g", _vp), ("ln_b", _vp)]
 
 
+class PoolField(C.Structure):
+    """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
+    _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
+                ("slot", C.c_int32), ("varlen", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64)]
+
+
+POOL_COPY, POOL_SUM, POOL_MEAN, POOL_MAX = 0, 1, 2, 3      # satrans_pool_field.combiner (SATRANS_POOL_*)
+POOL_MAX_LEN = 32                                           # SATRANS_POOL_MAX_LEN
+POOL_MAX_FIELDS = 64                                        # SATRANS_POOL_MAX_FIELDS
+
+
 class AdamHParams(C.Structure):
     """Mirror of `satrans_adam_hparams`."""
     _fields_ = [("lr_over_bc1", C.c_float), ("bc2_sqrt", C.c_float), ("beta1", C.c_float),
@@ -100,6 +111,10 @@ SIGNATURES = {
     "satrans_gather_fwd": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, _vp, _vp,
                                      _vp, _vp]),
     "satrans_gather_read_probe_floats": (C.c_int64, []),
+    "satrans_pool_argmax_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "satrans_pool_gather_fwd": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.POINTER(PoolField), C.c_int, C.c_int, C.c_int, _vp, C.c_int,
+                                          C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "satrans_pool_bwd": (C.c_int, [_vp, C.POINTER(PoolField), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "satrans_gather_read_probe": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp]),
     "satrans_set_layer_impl": (C.c_int, [C.c_int]),
     "satrans_layer_fused_supported": (C.c_int, [C.POINTER(LayerDesc)]),

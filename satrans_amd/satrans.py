@@ -15,6 +15,9 @@ import torch.nn as nn
 from .basemodel import BaseModel, make_embedding_tables
 from .inputs import DenseFeat, SparseFeat, split_columns
 
+POOL_MAX_LEN = 32          # csrc/pool.hip: SATRANS_POOL_MAX_LEN (the CPU side must not need the library to check it)
+POOL_MAX_FIELDS = 64       # ... SATRANS_POOL_MAX_FIELDS: sparse + varlen fields of a model with varlen fields
+
 
 class _MetaNetNorm(nn.Module):
     """Parameter holder for reference `MetaNet` (models/submodules.py:64-75): only its LayerNorm has parameters."""
@@ -83,8 +86,16 @@ class SATrans(BaseModel):
             raise TypeError("`flag` must be a string (the reference tests substrings of it, e.g. 'pos' in flag)")
         self.flag = flag
         sparse, dense, varlen = split_columns(dnn_feature_columns)
-        if varlen:
-            raise NotImplementedError("VarLenSparseFeat columns (reference main.py never passes any)")
+        if varlen and len(sparse) + len(varlen) > POOL_MAX_FIELDS:
+            raise ValueError(f"{len(sparse)} sparse + {len(varlen)} VarLenSparseFeat columns: a model with VarLenSparseFeat "
+                             f"columns takes at most {POOL_MAX_FIELDS} sparse + varlen fields (the pooled gather's field table)")
+        for c in varlen:
+            # pooled by csrc/pool.hip (deepctr-torch's SequencePoolingLayer: its modes, its ValueError)
+            if c.combiner not in ('sum', 'mean', 'max'):
+                raise ValueError(f"VarLenSparseFeat {c.name!r}: combiner {c.combiner!r}; parameter mode should in [sum, mean, max]")
+            if not 1 <= c.maxlen <= POOL_MAX_LEN:
+                raise ValueError(f"VarLenSparseFeat {c.name!r}: maxlen {c.maxlen} outside 1..{POOL_MAX_LEN} (the pooled gather "
+                                 f"keeps one mask bit per slot)")
         self.use_linear, self.use_dnn = use_linear, use_dnn
         self.num_domains_list = num_domains_list
         self.use_domain_dnn_linear = use_domain_dnn_linear
@@ -98,11 +109,12 @@ class SATrans(BaseModel):
         self.domain_column_list = domain_column_list
         embedding_size = self.embedding_size
         field_num = len(self.embedding_dict)
-        if field_num != len(sparse):
-            # the reference sizes dnn_linear by the number of distinct tables and then fails with a shape error in
-            # forward when two columns share an embedding_name; fail at construction instead of reading past the weight
-            raise ValueError(f"{len(sparse)} sparse columns share {field_num} embedding tables: SATrans needs one "
-                             f"embedding_name per column (dnn_linear is sized by the number of tables)")
+        if field_num != len(sparse) + len(varlen):
+            # the reference sizes dnn_linear by the number of distinct tables (varlen ones included, satrans.py:130,135,183) and
+            # then fails with a shape error in forward when two columns share an embedding_name; fail at construction instead of
+            # reading past the weight
+            raise ValueError(f"{len(sparse) + len(varlen)} sparse / varlen columns share {field_num} embedding tables: SATrans "
+                             f"needs one embedding_name per column (dnn_linear is sized by the number of tables)")
         dense_in = sum(c.dimension for c in linear_feature_columns if isinstance(c, DenseFeat))
         self.domain_embedding_dim = embedding_size
 
