@@ -266,13 +266,21 @@ int satrans_layer_fwd(const satrans_layer_desc* d, float* y, float* att, void* s
  * accumulation; LayerNorm, softmax and the attention dot products in fp32; weights rounded to bf16 once per workgroup while
  * they are staged into LDS).  BASELINE.json configs[1] "bf16 forward": predict / evaluate only - no dropout (SATRANS_TRAIN
  * must be clear), no attention capture; results differ from satrans_layer_fwd by bf16 rounding (~1e-2 on the logits).
- * Built for (D,U,H) = (32,64,4) and (64,128,4). */
+ * Built for
+ *   - the MetaNet form (or no modulation) at (D,U,H) = (32,64,4) and (64,128,4), the latter for F <= 64;
+ *   - SATRANS_GATE or SATRANS_BILINEAR at (D,H) = (32,4), any U (these flags have no MetaNet; U is ignored as in
+ *     satrans_layer_fused_supported): gate scales q / k by 2 * the generated row in fp32 on the projection's accumulators,
+ *     bilinear is one more bf16 product of q with the block-diagonal image of the H generated d x d maps;
+ *   with the field count as a constant (matrix-pipe attention) for F = 19 and F = 15, at run time otherwise; one or two generated
+ *   tables; x_rows.
+ * Refused (_supported answers 0, the launch returns SATRANS_E_UNSUPPORTED): SATRANS_TRAIN, SATRANS_GATE together with
+ * SATRANS_BILINEAR, either of them at any other (D,H) - (64,4) included: the general fp32 path serves it. */
 int satrans_layer_fwd_bf16_supported(const satrans_layer_desc* d);
 int satrans_layer_fwd_bf16(const satrans_layer_desc* d, float* y, void* stream);
 /* The whole stack of n layers (satrans.py:236-239: `for layer in self.domain_int_layers`) of an EVALUATION forward as one launch: a
  * tile's rows stay in LDS between the layers - read from HBM once, written once - and every layer's weight images are staged once
- * per workgroup; per layer the code of satrans_layer_fwd_bf16, i.e. the same bits.  1 <= n <= 4 layers of D = 32 with one shape,
- * one set of flags and one scenario bucketing; layer 0 reads its rows as satrans_layer_fwd_bf16 does (fused gather included), the
+ * per workgroup; per layer the code of satrans_layer_fwd_bf16, i.e. the same bits.  1 <= n <= 4 layers of D = 32 (every form
+ * satrans_layer_fwd_bf16 is built for at D = 32: MetaNet, gate, bilinear) with one shape, one set of flags and one scenario bucketing; layer 0 reads its rows as satrans_layer_fwd_bf16 does (fused gather included), the
  * x / x_rows of the others are ignored.  y: the last layer's output [B][F][D]. */
 int satrans_stack_fwd_bf16_supported(int n, const satrans_layer_desc* const* descs);
 int satrans_stack_fwd_bf16(int n, const satrans_layer_desc* const* descs, float* y, void* stream);

@@ -65,12 +65,53 @@ __device__ __forceinline__ void chain_bf16(const __bf16* __restrict__ il, const 
     }
 }
 
+// flag 'gate': the doubled generated rows of one scenario, fp32 (2 v is exact, so q0 * (2 v) has the bits of q0 * v * 2)
+__device__ __forceinline__ void stage_gate(const satrans_layer_desc& a, int scen, int D, bool meta_q, bool meta_k,
+                                           float* __restrict__ gq, float* __restrict__ gk) {
+    for (int i = threadIdx.x; i < D; i += blockDim.x) {
+        if (meta_q) gq[i] = 2.0f * a.tab_q[(size_t)scen * a.tab_stride + i];
+        if (meta_k) gk[i] = 2.0f * a.tab_k[(size_t)scen * a.tab_stride + i];
+    }
+}
+
+// flag 'bilinear': the generated row of one scenario = H maps [d][d] (q_h = q_h M[h]) -> ONE block-diagonal bf16 image [D][D + 8]
+// in the layout of stage_bf16, image row = output feature h d + j, contraction index = input feature h d + i.  Every element
+// of the image is written (zeros outside the blocks), so nothing of a previous scenario or of uninitialised LDS survives.
+template <int D, int H>
+__device__ __forceinline__ void stage_bilinear(const float* __restrict__ row, __bf16* __restrict__ img) {
+    constexpr int d = D / H, KD = D + 8;
+    for (int e = threadIdx.x; e < D * D; e += blockDim.x) {
+        const int k = e / D, o = e - k * D;          // input feature, output feature
+        const int h = k / d;
+        const float v = (o / d == h) ? row[h * d * d + (k - h * d) * d + (o - h * d)] : 0.f;
+        img[o * KD + bf16_pos(k)] = (__bf16)v;
+    }
+}
+
+// D-layout fragment (features 16 t + 4 g + r of the lane's token) times an LDS vector over the features
+template <int KT_>
+__device__ __forceinline__ void scale_frag(float (&v)[KT_][4], const float* __restrict__ vec, int g4) {
+#pragma unroll
+    for (int t = 0; t < KT_; ++t) {
+        const float4 s = *reinterpret_cast<const float4*>(vec + 16 * t + g4);
+        v[t][0] *= s.x; v[t][1] *= s.y; v[t][2] *= s.z; v[t][3] *= s.w;
+    }
+}
+
 // FT: the field count as a constant (0 = a.F).  With it and d = 8 the attention runs on the matrix pipe as in the fused backward
 // (layer_fused.hip, phases B / D / E): v_mfma_f32_4x4x1_16b_f32, one lane per (sample, head, query row) in whole groups of
 // FP = 4 ceil(F / 4) lanes per wave, S^T = K q from the key rows picked by lane & 3 and the lane's own query row, the softmax
 // lane-local on the accumulator registers, o = P V from the value feature pairs picked by lane & 3 - fp32 throughout.  With
 // the products on the bf16 pipe the attention is ~2/3 of this kernel, so this is where its time goes.
-template <int D, int U, int H, int WAVES, int FT = 0>
+// MOD: what modulates q / k (compile time, as in layer_fused.hip: the MetaNet instantiations pay nothing for the other two) -
+//   0  the MetaNet (or nothing);
+//   1  flag 'gate' (satrans.py:61-62,68-69): q, k *= 2 vec[scenario] in fp32 on the projection's accumulator registers, the doubled
+//      vectors formed once per scenario in LDS;
+//   2  flag 'bilinear' (satrans.py:79-81): q_h = q_h M[scenario, h], the H maps staged per scenario as ONE block-diagonal D x D bf16
+//      image in the bf16_pos layout - one more chain_bf16 product, the rounding model of every other product here.
+// 1 and 2 have no MetaNet, no MetaNet LayerNorm and no residual around it: their W1 / W2 images and lnq / lnk vectors are neither
+// carved out of LDS nor read (the tile chooser spends the room on samples), and U plays no part.
+template <int D, int U, int H, int WAVES, int FT = 0, int MOD = 0>
 __global__ __launch_bounds__(64 * WAVES) void layer_fwd_bf16_kernel(satrans_layer_desc a, int Tsamp, float* __restrict__ y) {
     constexpr int KT = D / 16, UT = U / 16, d = D / H, LD = D + 4, KD = D + 8, KU = U + 8;
     constexpr bool MFA = FT != 0 && d == 8;
@@ -78,7 +119,8 @@ __global__ __launch_bounds__(64 * WAVES) void layer_fwd_bf16_kernel(satrans_laye
     const int F = FT ? FT : a.F;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = lane & 15, g = lane >> 4, g4 = 4 * g;
-    const bool meta_q = a.flags & SATRANS_META_Q, meta_k = a.flags & SATRANS_META_K;
+    constexpr bool gate = MOD == 1, bilin = MOD == 2;
+    const bool meta_q = !bilin && (a.flags & SATRANS_META_Q), meta_k = !bilin && (a.flags & SATRANS_META_K);
     const bool same_tab = a.tab_q == a.tab_k;
     const bool relu_out = a.flags & SATRANS_RELU_OUT, use_res = !(a.flags & SATRANS_NO_RES);
 
@@ -86,12 +128,18 @@ __global__ __launch_bounds__(64 * WAVES) void layer_fwd_bf16_kernel(satrans_laye
     __bf16* bp = reinterpret_cast<__bf16*>(lds);
     auto take_b = [&](int cnt) { __bf16* r = bp; bp += (cnt + 7) & ~7; return r; };
     __bf16* wq = take_b(D * KD); __bf16* wk = take_b(D * KD); __bf16* wv = take_b(D * KD); __bf16* wo = take_b(D * KD);
-    __bf16* w1q = take_b(U * KD); __bf16* w2q = take_b(D * KU);
-    __bf16* w1k = same_tab ? w1q : take_b(U * KD);
-    __bf16* w2k = same_tab ? w2q : take_b(D * KU);
+    [[maybe_unused]] __bf16 *w1q = nullptr, *w2q = nullptr, *w1k = nullptr, *w2k = nullptr, *wb = nullptr;
+    if constexpr (MOD == 0) {
+        w1q = take_b(U * KD); w2q = take_b(D * KU);
+        w1k = same_tab ? w1q : take_b(U * KD);
+        w2k = same_tab ? w2q : take_b(D * KU);
+    }
+    if constexpr (bilin) wb = take_b(D * KD);       // wb[h d + j][h d + i] = M[scenario, h][i][j], zero outside the H blocks
     float* p = reinterpret_cast<float*>(bp);
     auto take = [&](int cnt) { float* r = p; p += (cnt + 3) & ~3; return r; };
-    float* lnq_g = take(D); float* lnq_b = take(D); float* lnk_g = take(D); float* lnk_b = take(D);
+    [[maybe_unused]] float *lnq_g = nullptr, *lnq_b = nullptr, *lnk_g = nullptr, *lnk_b = nullptr, *gq = nullptr, *gk = nullptr;
+    if constexpr (MOD == 0) { lnq_g = take(D); lnq_b = take(D); lnk_g = take(D); lnk_b = take(D); }
+    if constexpr (gate) { gq = take(D); gk = take(D); }      // 2 vec_q[scenario], 2 vec_k[scenario]
     float* ln_g = take(D); float* ln_b = take(D);
     const int rows = ((Tsamp * F + 15) >> 4) << 4;
     float* sq = take(rows * LD);
@@ -104,8 +152,10 @@ __global__ __launch_bounds__(64 * WAVES) void layer_fwd_bf16_kernel(satrans_laye
     stage_bf16(a.w_out, wo, D, D, KD, false);
     for (int i = threadIdx.x; i < D; i += blockDim.x) {
         ln_g[i] = a.ln_g[i]; ln_b[i] = a.ln_b[i];
-        if (meta_q) { lnq_g[i] = a.lnq_g[i]; lnq_b[i] = a.lnq_b[i]; }
-        if (meta_k) { lnk_g[i] = a.lnk_g[i]; lnk_b[i] = a.lnk_b[i]; }
+        if constexpr (MOD == 0) {
+            if (meta_q) { lnq_g[i] = a.lnq_g[i]; lnq_b[i] = a.lnq_b[i]; }
+            if (meta_k) { lnk_g[i] = a.lnk_g[i]; lnk_b[i] = a.lnk_b[i]; }
+        }
     }
     const int il_d = n * KD + 8 * g, il_u = n * KU + 8 * g;      // this lane's fragment inside an image with rows of D / U inputs
     const float inv_sqrt_d = 1.0f / sqrtf((float)d);
@@ -118,6 +168,7 @@ __global__ __launch_bounds__(64 * WAVES) void layer_fwd_bf16_kernel(satrans_laye
       pre += nt_s;
       if (t0 >= t1) continue;
       // ---- this scenario's generated MetaNet weights (the previous tile loop ended on a barrier) ------------------
+      if constexpr (MOD == 0) {
       if (meta_q) {
           const float* row = a.tab_q + (size_t)scen * a.tab_stride;
           stage_bf16(row, w1q, U, D, KD, true);               // W1 [D][U]: in-major, K = D
@@ -128,6 +179,9 @@ __global__ __launch_bounds__(64 * WAVES) void layer_fwd_bf16_kernel(satrans_laye
           stage_bf16(row, w1k, U, D, KD, true);
           stage_bf16(row + D * U, w2k, D, U, KU, true);
       }
+      }
+      if constexpr (gate) stage_gate(a, scen, D, meta_q, meta_k, gq, gk);
+      if constexpr (bilin) stage_bilinear<D, H>(a.tab_q + (size_t)scen * a.tab_stride, wb);
       __syncthreads();
       const int lo = a.seg[scen], hi = a.seg[scen + 1];
       for (int tile = t0; tile < t1; ++tile) {
@@ -146,6 +200,7 @@ __global__ __launch_bounds__(64 * WAVES) void layer_fwd_bf16_kernel(satrans_laye
             chain_bf16<KT, KT, KD>(wq + il_d, x, q);                                     // satrans.py:55-57
             chain_bf16<KT, KT, KD>(wk + il_d, x, k);
             chain_bf16<KT, KT, KD>(wv + il_d, x, v);
+            if constexpr (MOD == 0) {
             auto metanet = [&](float (&z)[KT][4], const __bf16* w1, const __bf16* w2, const float* gam, const float* bet) {
                 float h[UT][4], o[KT][4];                                                // submodules.py:77-103
                 chain_bf16<KT, UT, KD>(w1 + il_d, z, h);
@@ -163,6 +218,19 @@ __global__ __launch_bounds__(64 * WAVES) void layer_fwd_bf16_kernel(satrans_laye
             };
             if (meta_q) metanet(q, w1q, w2q, lnq_g, lnq_b);                              // satrans.py:60-66
             if (meta_k) metanet(k, w1k, w2k, lnk_g, lnk_b);                              // satrans.py:67-73
+            }
+            if constexpr (gate) {                                                        // satrans.py:61-62,68-69
+                if (meta_q) scale_frag<KT>(q, gq, g4);
+                if (meta_k) scale_frag<KT>(k, gk, g4);
+            }
+            if constexpr (bilin) {                                                       // satrans.py:79-81
+                float qb[KT][4];
+                chain_bf16<KT, KT, KD>(wb + il_d, q, qb);
+#pragma unroll
+                for (int t = 0; t < KT; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) q[t][r] = qb[t][r];
+            }
             store_frag<KT>(sq + (size_t)tok * LD + g4, q);
             store_frag<KT>(sk + (size_t)tok * LD + g4, k);
             store_frag<KT>(sv + (size_t)tok * LD + g4, v);
@@ -326,7 +394,7 @@ struct Bf16Head {
     float* logit;
 };
 
-template <int D, int U, int H, int WAVES, int FT = 0>
+template <int D, int U, int H, int WAVES, int FT = 0, int MOD = 0>
 __global__ __launch_bounds__(64 * WAVES) void stack_fwd_bf16_kernel(Bf16Stack sa, int Tsamp, float* __restrict__ y, Bf16Head hd) {
     const satrans_layer_desc& a = sa.d[0];      // shape, flags, scenario segments and the input rows: the first layer's
     const int NL = sa.L;
@@ -336,16 +404,20 @@ __global__ __launch_bounds__(64 * WAVES) void stack_fwd_bf16_kernel(Bf16Stack sa
     const int F = FT ? FT : a.F;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = lane & 15, g = lane >> 4, g4 = 4 * g;
-    const bool meta_q = a.flags & SATRANS_META_Q, meta_k = a.flags & SATRANS_META_K;
+    constexpr bool gate = MOD == 1, bilin = MOD == 2;
+    const bool meta_q = !bilin && (a.flags & SATRANS_META_Q), meta_k = !bilin && (a.flags & SATRANS_META_K);
     const bool same_tab = a.tab_q == a.tab_k;
     const bool relu_out = a.flags & SATRANS_RELU_OUT, use_res = !(a.flags & SATRANS_NO_RES);
 
     // ---- carve LDS: bf16 images first (16-byte aligned pieces), then fp32 vectors and the q / k / v row buffers ---------
     // per layer: four projection images, the MetaNet images of one or two tables, six LayerNorm vectors - NL equal blocks
-    const int per_b = 4 * D * KD + (same_tab ? 1 : 2) * (U * KD + D * KU);            // bf16 elements of a layer (multiples of 8)
+    // (gate: no MetaNet images, the two doubled gate vectors + two LayerNorm vectors; bilinear: one block-diagonal image, two vectors)
+    constexpr int NV = MOD == 0 ? 6 : (gate ? 4 : 2);                                  // fp32 vectors of a layer, the LayerNorm's last
+    const int per_b = MOD == 0 ? 4 * D * KD + (same_tab ? 1 : 2) * (U * KD + D * KU)   // bf16 elements of a layer (multiples of 8)
+                               : (bilin ? 5 : 4) * D * KD;
     __bf16* const img0 = reinterpret_cast<__bf16*>(lds);
     float* const vec0 = reinterpret_cast<float*>(img0 + (size_t)NL * per_b);
-    float* p = vec0 + NL * 6 * D;
+    float* p = vec0 + NL * NV * D;
     auto take = [&](int cnt) { float* r = p; p += (cnt + 3) & ~3; return r; };
     const int rows = ((Tsamp * F + 15) >> 4) << 4;
     float* sq = take(rows * LD);
@@ -360,11 +432,13 @@ __global__ __launch_bounds__(64 * WAVES) void stack_fwd_bf16_kernel(Bf16Stack sa
         stage_bf16(al.w_key, wq + D * KD, D, D, KD, true);
         stage_bf16(al.w_value, wq + 2 * D * KD, D, D, KD, true);
         stage_bf16(al.w_out, wq + 3 * D * KD, D, D, KD, false);
-        float* vec = vec0 + l * 6 * D;
+        float* vec = vec0 + l * NV * D;
         for (int i = threadIdx.x; i < D; i += blockDim.x) {
-            vec[4 * D + i] = al.ln_g[i]; vec[5 * D + i] = al.ln_b[i];
-            if (meta_q) { vec[i] = al.lnq_g[i]; vec[D + i] = al.lnq_b[i]; }
-            if (meta_k) { vec[2 * D + i] = al.lnk_g[i]; vec[3 * D + i] = al.lnk_b[i]; }
+            vec[(NV - 2) * D + i] = al.ln_g[i]; vec[(NV - 1) * D + i] = al.ln_b[i];
+            if constexpr (MOD == 0) {
+                if (meta_q) { vec[i] = al.lnq_g[i]; vec[D + i] = al.lnq_b[i]; }
+                if (meta_k) { vec[2 * D + i] = al.lnk_g[i]; vec[3 * D + i] = al.lnk_b[i]; }
+            }
         }
     }
     const int il_d = n * KD + 8 * g, il_u = n * KU + 8 * g;      // this lane's fragment inside an image with rows of D / U inputs
@@ -380,7 +454,10 @@ __global__ __launch_bounds__(64 * WAVES) void stack_fwd_bf16_kernel(Bf16Stack sa
       // ---- this scenario's generated MetaNet weights (the previous tile loop ended on a barrier) ------------------
       for (int l = 0; l < NL; ++l) {
           const satrans_layer_desc& al = sa.d[l];
-          __bf16* w1q = img0 + (size_t)l * per_b + 4 * D * KD;
+          [[maybe_unused]] __bf16* w1q = img0 + (size_t)l * per_b + 4 * D * KD;      // (bilinear: the block-diagonal image)
+          if constexpr (gate) stage_gate(al, scen, D, meta_q, meta_k, vec0 + l * NV * D, vec0 + l * NV * D + D);
+          if constexpr (bilin) stage_bilinear<D, H>(al.tab_q + (size_t)scen * al.tab_stride, w1q);
+          if constexpr (MOD == 0) {
           __bf16* w2q = w1q + U * KD;
           if (meta_q) {
               const float* row = al.tab_q + (size_t)scen * al.tab_stride;
@@ -392,6 +469,7 @@ __global__ __launch_bounds__(64 * WAVES) void stack_fwd_bf16_kernel(Bf16Stack sa
               __bf16* w1k = same_tab ? w1q : w2q + D * KU;
               stage_bf16(row, w1k, U, D, KD, true);
               stage_bf16(row + D * U, w1k + U * KD, D, U, KU, true);
+          }
           }
       }
       __syncthreads();
@@ -405,10 +483,16 @@ __global__ __launch_bounds__(64 * WAVES) void stack_fwd_bf16_kernel(Bf16Stack sa
         // this layer's images and vectors
         const __bf16* wq = img0 + (size_t)l * per_b;
         const __bf16* wk = wq + D * KD; const __bf16* wv = wk + D * KD; const __bf16* wo = wv + D * KD;
-        const __bf16* w1q = wo + D * KD; const __bf16* w2q = w1q + U * KD;
-        const __bf16* w1k = same_tab ? w1q : w2q + D * KU; const __bf16* w2k = w1k + U * KD;
-        const float* lnq_g = vec0 + l * 6 * D; const float* lnq_b = lnq_g + D; const float* lnk_g = lnq_b + D;
-        const float* lnk_b = lnk_g + D; const float* ln_g = lnk_b + D; const float* ln_b = ln_g + D;
+        // (gate / bilinear: the slot behind wo is the block-diagonal image, the first two vectors are the doubled gate vectors;
+        //  the MetaNet's names below are then never dereferenced)
+        [[maybe_unused]] const __bf16* w1q = wo + D * KD; [[maybe_unused]] const __bf16* w2q = w1q + U * KD;
+        [[maybe_unused]] const __bf16* w1k = same_tab ? w1q : w2q + D * KU; [[maybe_unused]] const __bf16* w2k = w1k + U * KD;
+        [[maybe_unused]] const __bf16* wb = w1q;
+        const float* vecl = vec0 + l * NV * D;
+        [[maybe_unused]] const float* lnq_g = vecl; [[maybe_unused]] const float* lnq_b = vecl + D;
+        [[maybe_unused]] const float* lnk_g = vecl + 2 * D; [[maybe_unused]] const float* lnk_b = vecl + 3 * D;
+        [[maybe_unused]] const float* gq = vecl; [[maybe_unused]] const float* gk = vecl + D;
+        const float* ln_g = vecl + (NV - 2) * D; const float* ln_b = ln_g + D;
         const bool first_l = l == 0, last_l = l == NL - 1;
         // ---- phase 1: projections + MetaNet per 16-token tile, all in registers --------------------------
         for (int tt = wave; tt < ntt; tt += WAVES) {
@@ -421,6 +505,7 @@ __global__ __launch_bounds__(64 * WAVES) void stack_fwd_bf16_kernel(Bf16Stack sa
             chain_bf16<KT, KT, KD>(wq + il_d, x, q);                                     // satrans.py:55-57
             chain_bf16<KT, KT, KD>(wk + il_d, x, k);
             chain_bf16<KT, KT, KD>(wv + il_d, x, v);
+            if constexpr (MOD == 0) {
             auto metanet = [&](float (&z)[KT][4], const __bf16* w1, const __bf16* w2, const float* gam, const float* bet) {
                 float h[UT][4], o[KT][4];                                                // submodules.py:77-103
                 chain_bf16<KT, UT, KD>(w1 + il_d, z, h);
@@ -438,6 +523,19 @@ __global__ __launch_bounds__(64 * WAVES) void stack_fwd_bf16_kernel(Bf16Stack sa
             };
             if (meta_q) metanet(q, w1q, w2q, lnq_g, lnq_b);                              // satrans.py:60-66
             if (meta_k) metanet(k, w1k, w2k, lnk_g, lnk_b);                              // satrans.py:67-73
+            }
+            if constexpr (gate) {                                                        // satrans.py:61-62,68-69
+                if (meta_q) scale_frag<KT>(q, gq, g4);
+                if (meta_k) scale_frag<KT>(k, gk, g4);
+            }
+            if constexpr (bilin) {                                                       // satrans.py:79-81
+                float qb[KT][4];
+                chain_bf16<KT, KT, KD>(wb + il_d, q, qb);
+#pragma unroll
+                for (int t = 0; t < KT; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) q[t][r] = qb[t][r];
+            }
             store_frag<KT>(sq + (size_t)tok * LD + g4, q);
             store_frag<KT>(sk + (size_t)tok * LD + g4, k);
             store_frag<KT>(sv + (size_t)tok * LD + g4, v);
@@ -610,20 +708,28 @@ __global__ __launch_bounds__(64 * WAVES) void stack_fwd_bf16_kernel(Bf16Stack sa
 }
 
 
-static int64_t bf16_fwd_lds_bytes(int T, int F, int D, int U, bool same_tab) {
-    const int64_t KD = D + 8, KU = U + 8, LD = D + 4;
+// bf16 elements of one layer's images / its fp32 vectors, as the kernels carve them (mod: the kernels' MOD)
+static int64_t bf16_layer_image_elems(int D, int U, bool same_tab, int mod) {
+    const int64_t KD = D + 8, KU = U + 8;
+    if (mod) return (mod == 2 ? 5 : 4) * D * KD;
+    return 4 * D * KD + (same_tab ? 1 : 2) * ((int64_t)U * KD + D * KU);
+}
+static int bf16_layer_vectors(int mod) { return mod == 0 ? 6 : (mod == 1 ? 4 : 2); }
+static int bf16_mod_of(const satrans_layer_desc* d) { return (d->flags & SATRANS_GATE) ? 1 : ((d->flags & SATRANS_BILINEAR) ? 2 : 0); }
+
+static int64_t bf16_fwd_lds_bytes(int T, int F, int D, int U, bool same_tab, int mod) {
+    const int64_t LD = D + 4;
     const int64_t rows = (((int64_t)T * F + 15) / 16) * 16;
-    const int64_t bf = 4 * D * KD + (same_tab ? 1 : 2) * ((int64_t)U * KD + D * KU);
-    return 2 * bf + 4 * (6 * D + 3 * rows * LD) + 256;
+    return 2 * bf16_layer_image_elems(D, U, same_tab, mod) + 4 * (bf16_layer_vectors(mod) * D + 3 * rows * LD) + 256;
 }
 
-template <int D, int U, int H, int WAVES, int FT = 0>
+template <int D, int U, int H, int WAVES, int FT = 0, int MOD = 0>
 static int launch_fwd_bf16(const satrans_layer_desc* d, float* y, hipStream_t stream) {
     const bool same_tab = d->tab_q == d->tab_k;
     int best = 0;
     double best_eff = 0.0;
     for (int t = 1; t <= 4 * WAVES; ++t) {
-        if (bf16_fwd_lds_bytes(t, d->F, D, U, same_tab) > 156 * 1024) break;
+        if (bf16_fwd_lds_bytes(t, d->F, D, U, same_tab, MOD) > 156 * 1024) break;
         const int tok = t * d->F, ntt = (tok + 15) / 16;
         double eff = (double)tok / (16.0 * ntt) * (double)ntt / (double)(ceil_div(ntt, WAVES) * WAVES);
         if (FT != 0) {
@@ -635,29 +741,28 @@ static int launch_fwd_bf16(const satrans_layer_desc* d, float* y, hipStream_t st
         if (eff >= best_eff) { best_eff = eff; best = t; }
     }
     SATRANS_REQUIRE(best > 0, SATRANS_E_UNSUPPORTED, "layer_fwd(bf16): F=%d does not fit LDS", d->F);
-    const size_t lds = (size_t)bf16_fwd_lds_bytes(best, d->F, D, U, same_tab);
+    const size_t lds = (size_t)bf16_fwd_lds_bytes(best, d->F, D, U, same_tab, MOD);
     static size_t attr_set = 0;
     if (lds > attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)layer_fwd_bf16_kernel<D, U, H, WAVES, FT>,
+        hipError_t e = hipFuncSetAttribute((const void*)layer_fwd_bf16_kernel<D, U, H, WAVES, FT, MOD>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         SATRANS_REQUIRE(e == hipSuccess, SATRANS_E_LAUNCH, "layer_fwd(bf16): LDS attribute: %s", hipGetErrorString(e));
         attr_set = lds;
     }
     const int64_t tiles = ceil_div(d->B, best) + d->S;
     const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)cu_count()));
-    layer_fwd_bf16_kernel<D, U, H, WAVES, FT><<<gx, 64 * WAVES, lds, stream>>>(*d, best, y);
+    layer_fwd_bf16_kernel<D, U, H, WAVES, FT, MOD><<<gx, 64 * WAVES, lds, stream>>>(*d, best, y);
     SATRANS_CHECK_LAUNCH("layer_fwd_bf16_kernel");
     return SATRANS_OK;
 }
 
-static int64_t bf16_stack_lds_bytes(int NL, int T, int F, int D, int U, bool same_tab) {
-    const int64_t KD = D + 8, KU = U + 8, LD = D + 4;
+static int64_t bf16_stack_lds_bytes(int NL, int T, int F, int D, int U, bool same_tab, int mod) {
+    const int64_t LD = D + 4;
     const int64_t rows = (((int64_t)T * F + 15) / 16) * 16;
-    const int64_t bf = 4 * D * KD + (same_tab ? 1 : 2) * ((int64_t)U * KD + D * KU);
-    return 2 * bf * NL + 4 * (6 * D * NL + 4 * rows * LD) + 256;
+    return 2 * bf16_layer_image_elems(D, U, same_tab, mod) * NL + 4 * (bf16_layer_vectors(mod) * D * NL + 4 * rows * LD) + 256;
 }
 
-template <int D, int U, int H, int WAVES, int FT = 0>
+template <int D, int U, int H, int WAVES, int FT = 0, int MOD = 0>
 static int launch_stack_bf16(const Bf16Stack& sa, float* y, const Bf16Head& hd, hipStream_t stream) {
     const satrans_layer_desc* d = &sa.d[0];
     const bool same_tab = d->tab_q == d->tab_k;
@@ -666,7 +771,7 @@ static int launch_stack_bf16(const Bf16Stack& sa, float* y, const Bf16Head& hd, 
     for (int t = 1; t <= 4 * WAVES; ++t) {
         // (the whole 160 KB of a CU: three AliCCP layers with a tile of nine samples - eleven 16-token tiles for twelve waves, exactly
         //  one round of 36 (sample, head) groups in the attention - come to 163,840 bytes with the alignment slack)
-        if (bf16_stack_lds_bytes(sa.L, t, d->F, D, U, same_tab) > 160 * 1024) break;
+        if (bf16_stack_lds_bytes(sa.L, t, d->F, D, U, same_tab, MOD) > 160 * 1024) break;
         const int tok = t * d->F, ntt = (tok + 15) / 16;
         double eff = (double)tok / (16.0 * ntt) * (double)ntt / (double)(ceil_div(ntt, WAVES) * WAVES);
         if (FT != 0) {
@@ -677,17 +782,17 @@ static int launch_stack_bf16(const Bf16Stack& sa, float* y, const Bf16Head& hd, 
         if (eff >= best_eff) { best_eff = eff; best = t; }
     }
     SATRANS_REQUIRE(best > 0, SATRANS_E_UNSUPPORTED, "stack_fwd(bf16): %d layers of F=%d do not fit LDS", sa.L, d->F);
-    const size_t lds = (size_t)bf16_stack_lds_bytes(sa.L, best, d->F, D, U, same_tab);
+    const size_t lds = (size_t)bf16_stack_lds_bytes(sa.L, best, d->F, D, U, same_tab, MOD);
     static size_t attr_set = 0;
     if (lds > attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)stack_fwd_bf16_kernel<D, U, H, WAVES, FT>,
+        hipError_t e = hipFuncSetAttribute((const void*)stack_fwd_bf16_kernel<D, U, H, WAVES, FT, MOD>,
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         SATRANS_REQUIRE(e == hipSuccess, SATRANS_E_LAUNCH, "stack_fwd(bf16): LDS attribute: %s", hipGetErrorString(e));
         attr_set = lds;
     }
     const int64_t tiles = ceil_div(d->B, best) + d->S;
     const int gx = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, (int64_t)cu_count()));
-    stack_fwd_bf16_kernel<D, U, H, WAVES, FT><<<gx, 64 * WAVES, lds, stream>>>(sa, best, y, hd);
+    stack_fwd_bf16_kernel<D, U, H, WAVES, FT, MOD><<<gx, 64 * WAVES, lds, stream>>>(sa, best, y, hd);
     SATRANS_CHECK_LAUNCH("stack_fwd_bf16_kernel");
     return SATRANS_OK;
 }
@@ -711,22 +816,34 @@ extern "C" int satrans_stack_fwd_bf16_supported(int n, const satrans_layer_desc*
             return 0;
     }
     const bool same_tab = descs[0]->tab_q == descs[0]->tab_k;
-    return bf16_stack_lds_bytes(n, 1, descs[0]->F, 32, 64, same_tab) <= 160 * 1024;
+    return bf16_stack_lds_bytes(n, 1, descs[0]->F, 32, 64, same_tab, bf16_mod_of(descs[0])) <= 160 * 1024;
+}
+
+// F = 19 (AliCCP) and F = 15 (Alimama) as constants - the matrix-pipe attention -, any other field count at run time
+template <int MOD>
+static int stack_fwd_bf16_mod(const Bf16Stack& sa, float* y, const Bf16Head& hd, hipStream_t stream) {
+    const int F = sa.d[0].F;
+    if (F == 19) return launch_stack_bf16<32, 64, 4, 12, 19, MOD>(sa, y, hd, stream);
+    if (F == 15) return launch_stack_bf16<32, 64, 4, 12, 15, MOD>(sa, y, hd, stream);
+    return launch_stack_bf16<32, 64, 4, 12, 0, MOD>(sa, y, hd, stream);
 }
 
 static int stack_fwd_bf16_any(int n, const satrans_layer_desc* const* descs, float* y, const Bf16Head& hd, hipStream_t stream) {
     Bf16Stack sa;
     for (int l = 0; l < 4; ++l) sa.d[l] = *descs[l < n ? l : 0];
     sa.L = n;
-    const satrans_layer_desc* d = descs[0];
-    if (d->F == 19) return launch_stack_bf16<32, 64, 4, 12, 19>(sa, y, hd, stream);      // AliCCP
-    if (d->F == 15) return launch_stack_bf16<32, 64, 4, 12, 15>(sa, y, hd, stream);      // Alimama
-    return launch_stack_bf16<32, 64, 4, 12>(sa, y, hd, stream);
+    const int mod = bf16_mod_of(descs[0]);
+    if (mod == 1) return stack_fwd_bf16_mod<1>(sa, y, hd, stream);
+    if (mod == 2) return stack_fwd_bf16_mod<2>(sa, y, hd, stream);
+    return stack_fwd_bf16_mod<0>(sa, y, hd, stream);
 }
 
+static const char kBf16StackBuilt[] =
+    "1 - 4 evaluation layers of one shape, flags and scenario bucketing: (D,U,H) = (32,64,4) MetaNet, or (D,H) = (32,4) with gate "
+    "or bilinear (not both, any U)";
+
 extern "C" int satrans_stack_fwd_bf16(int n, const satrans_layer_desc* const* descs, float* y, void* stream_) {
-    SATRANS_REQUIRE(satrans_stack_fwd_bf16_supported(n, descs), SATRANS_E_UNSUPPORTED,
-                    "stack_fwd(bf16): 1 - 4 evaluation layers of (D,U,H) = (32,64,4), one shape, flags and scenario bucketing");
+    SATRANS_REQUIRE(satrans_stack_fwd_bf16_supported(n, descs), SATRANS_E_UNSUPPORTED, "stack_fwd(bf16): %s", kBf16StackBuilt);
     SATRANS_REQUIRE(y, SATRANS_E_BADARG, "stack_fwd(bf16): null output");
     Bf16Head hd = {};
     return stack_fwd_bf16_any(n, descs, y, hd, (hipStream_t)stream_);
@@ -735,8 +852,7 @@ extern "C" int satrans_stack_fwd_bf16(int n, const satrans_layer_desc* const* de
 // ... with the head: h->w [F*D + n_dense], h->bias, h->dense / dense_stride / h_dense_cols (HOST array, n_dense <= 2) as in
 // satrans_layer_bwd_head; outputs h->prob [B] and h->logit [B] (optional).  The last layer's rows are not written anywhere.
 extern "C" int satrans_stack_fwd_bf16_head(int n, const satrans_layer_desc* const* descs, const satrans_head_desc* h, void* stream_) {
-    SATRANS_REQUIRE(satrans_stack_fwd_bf16_supported(n, descs), SATRANS_E_UNSUPPORTED,
-                    "stack_fwd_head(bf16): 1 - 4 evaluation layers of (D,U,H) = (32,64,4), one shape, flags and scenario bucketing");
+    SATRANS_REQUIRE(satrans_stack_fwd_bf16_supported(n, descs), SATRANS_E_UNSUPPORTED, "stack_fwd_head(bf16): %s", kBf16StackBuilt);
     SATRANS_REQUIRE(h && h->w && h->bias && h->prob && h->n_dense >= 0 && h->n_dense <= 2 && (h->n_dense == 0 || (h->dense && h->h_dense_cols)),
                     SATRANS_E_BADARG, "stack_fwd_head(bf16): bad head operands");
     Bf16Head hd = {};
@@ -746,21 +862,35 @@ extern "C" int satrans_stack_fwd_bf16_head(int n, const satrans_layer_desc* cons
     return stack_fwd_bf16_any(n, descs, nullptr, hd, (hipStream_t)stream_);
 }
 
+// gate / bilinear replace the MetaNet (U plays no part, as in satrans_layer_fused_supported): built at (D, H) = (32, 4); both
+// together are no variant of the reference (satrans.py:61-64 takes the first)
 extern "C" int satrans_layer_fwd_bf16_supported(const satrans_layer_desc* d) {
-    if (!d || (d->flags & (SATRANS_GATE | SATRANS_BILINEAR | SATRANS_TRAIN))) return 0;
+    if (!d || (d->flags & SATRANS_TRAIN)) return 0;
+    const bool gate = d->flags & SATRANS_GATE, bilin = d->flags & SATRANS_BILINEAR;
+    if (gate && bilin) return 0;
+    if (gate || bilin) return d->D == 32 && d->H == 4;
     const bool meta = d->flags & (SATRANS_META_Q | SATRANS_META_K);
     if (d->D == 32 && d->H == 4 && (!meta || d->U == 64)) return 1;
     if (d->D == 64 && d->H == 4 && (!meta || d->U == 128) && d->F <= 64) return 1;
     return 0;
 }
 
+template <int MOD>
+static int layer_fwd_bf16_mod(const satrans_layer_desc* d, float* y, hipStream_t stream) {
+    if (d->F == 19) return launch_fwd_bf16<32, 64, 4, 12, 19, MOD>(d, y, stream);      // AliCCP
+    if (d->F == 15) return launch_fwd_bf16<32, 64, 4, 12, 15, MOD>(d, y, stream);      // Alimama
+    return launch_fwd_bf16<32, 64, 4, 12, 0, MOD>(d, y, stream);
+}
+
 extern "C" int satrans_layer_fwd_bf16(const satrans_layer_desc* d, float* y, void* stream_) {
     SATRANS_REQUIRE(satrans_layer_fwd_bf16_supported(d), SATRANS_E_UNSUPPORTED,
-                    "layer_fwd(bf16): evaluation forward of (D,U,H) = (32,64,4) or (64,128,4) without gate / bilinear");
+                    "layer_fwd(bf16): evaluation forward (SATRANS_TRAIN clear) of (D,U,H) = (32,64,4) or (64,128,4) MetaNet, or of "
+                    "(D,H) = (32,4) with gate or bilinear (not both, any U)");
     SATRANS_REQUIRE(y, SATRANS_E_BADARG, "layer_fwd(bf16): null output");
     hipStream_t stream = (hipStream_t)stream_;
-    if (d->D == 32 && d->F == 19) return launch_fwd_bf16<32, 64, 4, 12, 19>(d, y, stream);      // AliCCP
-    if (d->D == 32 && d->F == 15) return launch_fwd_bf16<32, 64, 4, 12, 15>(d, y, stream);      // Alimama
-    if (d->D == 32) return launch_fwd_bf16<32, 64, 4, 12>(d, y, stream);
+    const int mod = bf16_mod_of(d);
+    if (mod == 1) return layer_fwd_bf16_mod<1>(d, y, stream);
+    if (mod == 2) return layer_fwd_bf16_mod<2>(d, y, stream);
+    if (d->D == 32) return layer_fwd_bf16_mod<0>(d, y, stream);
     return launch_fwd_bf16<64, 128, 4, 8>(d, y, stream);
 }
