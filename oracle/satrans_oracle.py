@@ -409,6 +409,30 @@ def bce_sum(prob: Tensor, y: Tensor) -> Tensor:
 # --------------------------------------------------------------------------------------
 # Sibling users of the same kernels; test infrastructure like everything above
 # --------------------------------------------------------------------------------------
+# Test instrumentation for the siblings, in the manner of KINK_PROBE: when a dict {"eps": e, "near_zero": 0} is installed here,
+# selfattention_layer() counts the elements of t = drop(o) + x W_Res and meta_transformation() the hidden units x @ W1 whose
+# magnitude lies within e * (largest magnitude of that tensor) of the ReLU's kink.  An element that is EXACTLY zero is not
+# counted: it is a dropped element without a residual or a row of zeros, which every evaluation order computes as the same
+# exact zero and puts on the same (zero-gradient) branch.  Off (None) by default; the functions then do no extra work.
+SIBLING_KINK_PROBE: Optional[Dict] = None
+
+
+def _probe_sibling_kinks(t: Tensor) -> None:
+    if SIBLING_KINK_PROBE is not None:
+        ta = t.detach().abs()
+        SIBLING_KINK_PROBE["near_zero"] += int(((ta <= SIBLING_KINK_PROBE["eps"] * float(ta.max())) & (ta > 0)).sum())
+
+
+def sibling_dropout_masks(seed: int, step: int, B: int, Fn: int, D: int, H: int = 1) -> Dict:
+    """The masks of one training forward of satrans_amd.layers.SelfAttention_Layer / MetaTransformation for
+    `Dropper('masks', 0.1, ...)`: seed, step = the module's `_clock.seed`, `_clock.step` AFTER that forward; layer 0 and
+    p = 0.1 as layers.py sets them.  Self-attention reads (0, 'attn') and (0, 'out'), the MetaNet (0, 'metaQ') (H = 1).
+    The attention mask comes head-major, [H,B,F,F], as selfattention_layer stacks its heads (layer_forward: [B,H,F,F])."""
+    masks = dropout_masks(seed, step, B, Fn, D, H, 1, 0.1)
+    masks[(0, "attn")] = masks[(0, "attn")].permute(1, 0, 2, 3).contiguous()
+    return masks
+
+
 def selfattention_layer(P: Dict[str, Tensor], x: Tensor, head_num: int, use_res: bool = True, scaling: bool = True,
                         drop: Optional[Dropper] = None) -> Tuple[Tensor, Tensor]:
     """models/submodules.py:209-236 (SelfAttention_Layer.forward): q,k,v = x W; heads = contiguous chunks of D/H channels;
@@ -428,6 +452,7 @@ def selfattention_layer(P: Dict[str, Tensor], x: Tensor, head_num: int, use_res:
     o = drop(o, 0, "out")
     if use_res:
         o = o + x @ P["W_Res"]
+    _probe_sibling_kinks(o)
     o = torch.relu(o)
     return F.layer_norm(o, (D,), P["layer_norm.weight"], P["layer_norm.bias"], 1e-6), att
 
@@ -441,7 +466,9 @@ def meta_transformation(P: Dict[str, Tensor], ids: Tensor, x: Tensor, units: Lis
     D, U = units[0], units[1]
     W1 = vec[:, :D * U].reshape(-1, D, U)
     W2 = vec[:, D * U:D * U + U * units[2]].reshape(-1, U, units[2])
-    y = drop(torch.relu(x @ W1) @ W2, 0, "meta_q") + x
+    h = x @ W1
+    _probe_sibling_kinks(h)
+    y = drop(torch.relu(h) @ W2, 0, "metaQ") + x          # the site key of dropout_masks (kSiteMetaQ)
     if use_norm:
         y = F.layer_norm(y, (D,), P["ffn_layer_norm.weight"], P["ffn_layer_norm.bias"], 1e-6)
     return y

@@ -149,3 +149,87 @@ def test_meta_transformation_shape_sweep_against_the_oracle(D, U, use_norm):
         want = leaves[k].grad
         assert want is not None, k
         close(p.grad.cpu().numpy(), want.numpy(), 1e-4, k)
+
+
+# ---- the siblings' oracle in training mode and its kink probe (test infrastructure; no GPU) -------------------------------------
+def _small_selfatt(seed=3, B=4, F=7, D=16):
+    g = torch.Generator().manual_seed(seed)
+    P = {k: torch.randn(D, D, generator=g, dtype=torch.float64) * 0.3 for k in ("W_Query", "W_Key", "W_Value", "W_Res")}
+    P["layer_norm.weight"] = 1.0 + 0.2 * torch.randn(D, generator=g, dtype=torch.float64)
+    P["layer_norm.bias"] = 0.1 * torch.randn(D, generator=g, dtype=torch.float64)
+    return P, torch.randn(B, F, D, generator=g, dtype=torch.float64)
+
+
+def _small_metanet(seed=4, B=6, F=5, D=16, U=32, S=3):
+    g = torch.Generator().manual_seed(seed)
+    P = {"domain_embeddings.weight": torch.randn(S, D, generator=g, dtype=torch.float64),
+         "domain_map_dnn.weight": torch.randn(2 * D * U, D, generator=g, dtype=torch.float64) * 0.3,
+         "domain_map_dnn.bias": torch.randn(2 * D * U, generator=g, dtype=torch.float64) * 0.1,
+         "ffn_layer_norm.weight": torch.ones(D, dtype=torch.float64), "ffn_layer_norm.bias": torch.zeros(D, dtype=torch.float64)}
+    return P, torch.tensor([0, 2, 2, 1, 0, 2])[:B], torch.randn(B, F, D, generator=g, dtype=torch.float64)
+
+
+@pytest.mark.parametrize("H", [1, 2])
+def test_oracle_selfattention_replays_the_sibling_masks(H):
+    P, x = _small_selfatt()
+    B, F, D = x.shape
+    y0, a0 = O.selfattention_layer(P, x, H)
+    masks = O.sibling_dropout_masks(1234, 1, B, F, D, H)
+    assert masks[(0, "attn")].shape == (H, B, F, F) and masks[(0, "out")].shape == (B, F, D)
+    for m in masks.values():                          # keep -> 1 / (1 - p), drop -> 0, about one in ten dropped
+        assert set(np.unique(m.numpy())) == {np.float32(0.0), np.float32(1.0 / 0.9)}
+    y1, a1 = O.selfattention_layer(P, x, H, drop=O.Dropper("masks", 0.1, masks))
+    assert not torch.equal(y1, y0) and torch.isfinite(y1).all()
+    assert torch.equal(a1, a0 * masks[(0, "attn")].double())
+    # the mask of head h, sample b is the layer's [b, h] one: element index (h F + i) * pad4(F) + j of sample b
+    h, b, i, j = H - 1, 2, 3, 5
+    keep = O.dropout_keep(1234, 1, 0, 2, np.uint32(b), np.uint32((h * F + i) * ((F + 3) & ~3) + j), 0.1)
+    assert bool(keep) == bool(masks[(0, "attn")][h, b, i, j] > 0)
+    y2, _ = O.selfattention_layer(P, x, H, drop=O.Dropper("masks", 0.1, O.sibling_dropout_masks(1234, 2, B, F, D, H)))
+    assert not torch.equal(y2, y1)                    # the next step: other masks
+    ones = {k: torch.ones_like(m) for k, m in masks.items()}
+    y3, a3 = O.selfattention_layer(P, x, H, drop=O.Dropper("masks", 0.1, ones))
+    assert torch.equal(y3, y0) and torch.equal(a3, a0)
+
+
+@pytest.mark.parametrize("use_norm", [True, False])
+def test_oracle_meta_transformation_replays_the_sibling_masks(use_norm):
+    P, ids, x = _small_metanet()
+    B, F, D = x.shape
+    y0 = O.meta_transformation(P, ids, x, [D, 32, D], use_norm)
+    masks = O.sibling_dropout_masks(99, 1, B, F, D)
+    y1 = O.meta_transformation(P, ids, x, [D, 32, D], use_norm, drop=O.Dropper("masks", 0.1, masks))      # (raised KeyError 'meta_q')
+    assert not torch.equal(y1, y0) and torch.isfinite(y1).all()
+    if not use_norm:                                  # y - x = mask * (the MetaNet's output): zero exactly where dropped
+        dropped = masks[(0, "metaQ")] == 0
+        assert dropped.any() and torch.equal((y1 - x)[dropped], torch.zeros(int(dropped.sum()), dtype=torch.float64))
+    ones = {k: torch.ones_like(m) for k, m in masks.items()}
+    assert torch.equal(O.meta_transformation(P, ids, x, [D, 32, D], use_norm, drop=O.Dropper("masks", 0.1, ones)), y0)
+
+
+def test_sibling_kink_probe_counts_planted_elements_and_changes_nothing():
+    # self-attention with W_Value = 0 and W_Res = 1: t = x
+    P, x = _small_selfatt()
+    D = x.shape[-1]
+    P["W_Value"] = torch.zeros(D, D, dtype=torch.float64)
+    P["W_Res"] = torch.eye(D, dtype=torch.float64)
+    x[0, 0, 0], x[1, 2, 3], x[2, 4, 5] = 1e-7, -2e-7, 0.0          # two within 2e-6 * max|t| of the kink; an exact zero is not one
+    assert float(x.abs().max()) > 1.0 and int(((x.abs() < 1e-5) & (x != 0)).sum()) == 2
+    assert O.SIBLING_KINK_PROBE is None
+    off = O.selfattention_layer(P, x, 2)
+    O.SIBLING_KINK_PROBE = {"eps": 2e-6, "near_zero": 0}
+    try:
+        on = O.selfattention_layer(P, x, 2)
+        assert O.SIBLING_KINK_PROBE["near_zero"] == 2
+        # MetaNet with W1 = 1 (bias of the scenario encoder, weight 0): hidden = x
+        Pm, ids, xm = _small_metanet(D=16, U=16)
+        Pm["domain_map_dnn.weight"] = torch.zeros_like(Pm["domain_map_dnn.weight"])
+        Pm["domain_map_dnn.bias"][:256] = torch.eye(16, dtype=torch.float64).reshape(-1)
+        xm[3, 1, 2] = 3e-7
+        O.SIBLING_KINK_PROBE["near_zero"] = 0
+        m_on = O.meta_transformation(Pm, ids, xm, [16, 16, 16], True)
+        assert O.SIBLING_KINK_PROBE["near_zero"] == 1
+    finally:
+        O.SIBLING_KINK_PROBE = None
+    assert torch.equal(on[0], off[0]) and torch.equal(on[1], off[1])
+    assert torch.equal(O.meta_transformation(Pm, ids, xm, [16, 16, 16], True), m_on)
