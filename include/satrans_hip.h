@@ -34,7 +34,8 @@ extern "C" {
 /* 7: the scenario attention statistics (satrans_attn_stats_workspace_bytes, satrans_attn_stats_accumulate); no struct changed. */
 /*    Also in 7, added later: the pooled gather of VarLenSparseFeat fields and its backward (satrans_pool_field,
  *    satrans_pool_gather_fwd, satrans_pool_bwd, satrans_pool_argmax_bytes).  Purely additive - no existing struct or entry point
- *    changed - so a caller built against the earlier version-7 header runs unchanged; the binding checks the new symbols at load. */
+ *    changed - so a caller built against the earlier version-7 header runs unchanged; the binding checks the new symbols at load.
+ *    Likewise the instance-level attention search (satrans_attn_rule, satrans_attn_match, satrans_attn_inst_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -601,6 +602,68 @@ int satrans_sum_f64(const double* v, int64_t count, double* out, int accumulate,
 int64_t satrans_attn_stats_workspace_bytes(int B, int H, int F, int K);
 int satrans_attn_stats_accumulate(const float* att, const int32_t* key, int B, int H, int F, int K, double* acc,
                                   void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Instance-level attention search: predict's `inst_attn_dict` and `instattn` branches (reference models/meta_basemodel.py:
+ * 440-445, 460-499).  The (sample, head) pairs of a batch whose map of one layer satisfies a rule are found on the device and only
+ * their maps, probabilities and input rows are copied out.  Added under ABI 7: new entry points and new struct types only.
+ *
+ * A rule is a conjunction of 1..8 clauses, a clause a disjunction of 1..4 atoms, an atom `att[h, b, q, k] > thr`: strict, in
+ * fp32, never true for a NaN.  The reference's second rule, `A and (B or C)`, is two clauses of one and two atoms. */
+#define SATRANS_ATTN_MAX_RULES 8
+#define SATRANS_ATTN_MAX_CLAUSES 8
+#define SATRANS_ATTN_MAX_ATOMS 4
+#define SATRANS_ATTN_MAX_HEADS 16
+
+typedef struct {
+    int32_t q, k; /* query and key field, both in [0, F) */
+    float thr;    /* finite */
+} satrans_attn_atom;
+
+typedef struct {
+    int32_t n_clauses;                         /* 1..SATRANS_ATTN_MAX_CLAUSES */
+    int32_t n_atoms[SATRANS_ATTN_MAX_CLAUSES]; /* 1..SATRANS_ATTN_MAX_ATOMS for the clauses in use */
+    satrans_attn_atom atoms[SATRANS_ATTN_MAX_CLAUSES][SATRANS_ATTN_MAX_ATOMS];
+} satrans_attn_rule;
+
+typedef struct {
+    int64_t index; /* global sample index: first_index + the sample's position in its batch */
+    int32_t head;
+    int32_t rule; /* the rule that matched (the caller's choice, e.g. -1, in a hand-built list) */
+} satrans_attn_match;
+
+/* satrans_attn_inst_match: append one record per (sample b, head h, rule r) with rule r true on att[h, b] to a device list.
+ *   att      [H, B, F, F] one layer's attention as satrans_layer_fwd / satrans_layer_fwd_generic write it
+ *   rules    HOST array of n_rules (1..8) rules, copied by value into the launch; validated here (fields in [0, F), finite
+ *            thresholds, counts within bounds): a bad rule is SATRANS_E_BADARG, never a device fault
+ *   eligible optional [B] uint8: bit r set = rule r may match sample b (0: the sample matches nothing, 0xff: every rule may;
+ *            NULL: all of them) - label and column filters, evaluated by the caller
+ *   records  the list, `capacity` entries in all; total [1] int64 on the device = the records found so far, by this and earlier
+ *            calls.  The call appends at position total[0] while that is below `capacity` (the capacity left is capacity -
+ *            total[0], taken on the device: no host read between batches) and advances total[0] by EVERY match, beyond the
+ *            capacity too: total[0] > capacity afterwards means the list is truncated, and total[0] stays exact.
+ *   range    optional [2] int64 on the device: the list positions this call filled, clamped to the capacity
+ * Order within a call: sample, then head, then rule - with first_index = the batch's offset the list of a pass does not depend
+ * on the batch size.  (Deviation: the reference loops head-major inside each batch.)  Deterministic: one lane per pair, per-wave
+ * counts, one workgroup scans them, records written at the scanned offsets; no atomics.  A lane reads only the atoms its rules
+ * name (short-circuit).  Any F (odd included), any B, H in 1..16, B * H < 2^28.
+ *
+ * satrans_attn_inst_gather: for the records m of [m0, m1) (intersected with range[0..2) when `range`, a device pointer, is
+ * given) whose index lies in [first_index, first_index + B): maps[m] = att[head, index - first_index] (F * F dwords, bit for bit),
+ * pred[m] = prob[index - first_index], x_rows[m] = the first row_dwords dwords of row index - first_index of x (rows
+ * x_stride_dwords apart; any id dtype).  maps, pred and x_rows are each optional and indexed by LIST position.  Records of other
+ * batches or with a head outside [0, H) are skipped.  The same call serves hand-built lists (every head of chosen samples).
+ *
+ * workspace of _match: satrans_attn_inst_workspace_bytes(B, H, F) bytes (-1 on bad sizes).  satrans_attn_inst_check_rules runs
+ * the validation alone (no device). */
+int64_t satrans_attn_inst_workspace_bytes(int B, int H, int F);
+int satrans_attn_inst_check_rules(const satrans_attn_rule* rules, int n_rules, int F);
+int satrans_attn_inst_match(const float* att, int B, int H, int F, const satrans_attn_rule* rules, int n_rules,
+                            const uint8_t* eligible, int64_t first_index, satrans_attn_match* records, int64_t capacity,
+                            int64_t* total, int64_t* range, void* workspace, int64_t workspace_bytes, void* stream);
+int satrans_attn_inst_gather(const float* att, int B, int H, int F, const satrans_attn_match* records, int64_t m0, int64_t m1,
+                             const int64_t* range, int64_t first_index, float* maps, const float* prob, float* pred,
+                             const void* x, int64_t x_stride_dwords, int row_dwords, void* x_rows, void* stream);
 
 /* The per-step training metrics of fit(verbose > 0) (meta_basemodel.py:330-337: sklearn log_loss and roc_auc_score on host
  * copies of every batch) for one batch in one launch: out[0] = log_loss(y, p.astype(float64)) (probabilities clipped to

@@ -731,22 +731,59 @@ class BaseModel(nn.Module):
         return {"auc": auc, "domain_auc": per, "loss": loss, "pred": pred}
 
     def predict(self, x, batch_size=256, y=None, domain_ids=None):
-        """float64 [N,1] probabilities; models/meta_basemodel.py:401-517 (without the instattn paper-figure branch).
+        """float64 [N,1] probabilities; models/meta_basemodel.py:401-517.
 
         With 'showattn' in the flag (reference :421-426, 439-458, 506-514) the call also leaves the scenario-specific attention
         maps on the model: `attn_list_pos` / `attn_list_neg` / `attn_list_all`, lists [L][S] of float32 numpy [H, F, F] (S =
         num_domains_list[0]), the mean `normalized_att_scores` of the samples of scenario j (domain id j + bias, bias = 1 when
-        min(domain_ids) == 1) with y == 1 / y == 0 / any label, and `inst_attn_dict = []`; see attention_statistics().  `y` is
-        required there; `domain_ids` defaults to the model's first scenario column of `x`.  Deviation from the reference: an
-        empty (scenario, class) pair gives an all-NaN map where the reference crashes."""
+        min(domain_ids) == 1) with y == 1 / y == 0 / any label; see attention_statistics().  `y` is required there; `domain_ids`
+        defaults to the model's first scenario column of `x`.  Deviation from the reference: an empty (scenario, class) pair gives
+        an all-NaN map where the reference crashes.
+
+        `inst_attn_dict` (reference :440-445) is the list of float32 [H, F, F] layer-0 maps of the samples named by
+        `self.test_visual_ids`, in sample order - what the reference intends behind its stray `break`; [] without that attribute.
+
+        With 'instattn' in the flag as well (reference :460-499) the samples whose layer-0 attention satisfies one of
+        `self.instattn_rules` (attn_inst.AttentionRule objects; a ValueError names the attribute when it is missing - the reference
+        hard-codes two rules over Alimama's columns and a `classes_` attribute nothing sets, see examples/alimama_instattn.py) are
+        written to ./inst_attn_{flag}.txt, three lines per match: `score {pred},label {label},rule {r},head {h},index {i}`, the
+        F*F map values comma-joined with the reference's trailing comma, and the input row in the same style
+        (attn_inst.write_instances).  The result is also kept as `self.inst_attn_matches` (see attention_instances()).
+        Deviation: matches are listed by sample, then head, then rule, whatever the batch size; the reference's head-major
+        order inside each batch depends on it.  All of it is one pass: the search and the copies read the statistics' attention
+        buffer on the device right behind layer 0, and `attn_list_*` come out the same bits as with 'showattn' alone."""
         if self.flag and 'showattn' in self.flag:
-            pred, st = self._attention_pass(x, y, domain_ids, batch_size)
+            from . import attn_inst as AI
+            engine = self._require_engine()
+            visual = getattr(self, "test_visual_ids", None)
+            ctx_ids = ctx_rules = rules = None
+            if visual is not None and len(visual):
+                n_rows = self._n_rows(x)
+                ids = np.unique(np.asarray(list(visual), dtype=np.int64))
+                ids = ids[(ids >= 0) & (ids < n_rows)]                  # (the reference's `idx in test_visual_ids`)
+                if len(ids):
+                    ctx_ids = AI.AttentionInstances(engine, None, 0, records=AI.hand_records(ids, engine.H))
+            if 'instattn' in self.flag:
+                rules = getattr(self, "instattn_rules", None)
+                if not rules:
+                    raise ValueError("flag 'instattn': set model.instattn_rules to a list of attn_inst.AttentionRule objects "
+                                     "(the reference's own two rules are in examples/alimama_instattn.py)")
+                rules = list(rules)
+                ctx_rules = AI.AttentionInstances(engine, AI.resolve_rules(rules, AI.layer_field_names(self)), 0,
+                                                  int(getattr(self, "instattn_max_instances", 65536)))
+            pred, st = self._attention_pass(x, y, domain_ids, batch_size, ctx_ids, ctx_rules, rules)
             mean = st["mean"].astype(np.float32)
             L, S = mean.shape[0], mean.shape[1]
             self.attn_list_pos = [[mean[i, j, 0] for j in range(S)] for i in range(L)]
             self.attn_list_neg = [[mean[i, j, 1] for j in range(S)] for i in range(L)]
             self.attn_list_all = [[mean[i, j, 2] for j in range(S)] for i in range(L)]
-            self.inst_attn_dict = []                # (the reference's `break` at meta_basemodel.py:442 keeps it empty)
+            self.inst_attn_dict = []
+            if ctx_ids is not None:
+                maps = ctx_ids.result()["attention"]
+                self.inst_attn_dict = [maps[i:i + engine.H] for i in range(0, maps.shape[0], engine.H)]
+            if ctx_rules is not None:
+                self.inst_attn_matches = ctx_rules.result(y)
+                AI.write_instances(f'./inst_attn_{self.flag}.txt', self.inst_attn_matches)
             return pred
         return self._predict_pass(x, batch_size)
 
@@ -760,7 +797,38 @@ class BaseModel(nn.Module):
         layer kernels whatever set_forward_precision chose.  Sums and counts are additive across shards of the data."""
         return self._attention_pass(x, y, domain_ids, batch_size)[1]
 
-    def _attention_pass(self, x, y, domain_ids, batch_size):
+    def attention_instances(self, x, y=None, rules=None, sample_ids=None, layer=0, batch_size=256, max_instances=65536) -> dict:
+        """Instance-level attention of layer `layer`, selected on the device (csrc/attn_inst.hip); only the selection reaches the
+        host.  Either `rules` (1..8 attn_inst.AttentionRule: every (sample, head) pair whose map satisfies a rule and whose label
+        / input columns pass the rule's filters) or `sample_ids` (every head of those samples, in the given order, rule = -1).
+        -> {"index": int64 [M], "head": int32 [M], "rule": int32 [M], "pred": float64 [M] (predict's value of the sample),
+        "label": y[index] (when y is given), "attention": float32 [M, F, F] (the bits of `normalized_att_scores`[head, index]),
+        "x": [M, C] the samples' rows of the input matrix as the kernels read it, "total": the exact number of matches,
+        "truncated": total > max_instances (the first max_instances matches are returned)}.
+        Matches are ordered by sample index, then head, then rule: independent of batch_size.  The evaluation runs on the fp32
+        layer kernels whatever set_forward_precision chose; resident and streamed input give the same result."""
+        from . import attn_inst as AI
+        if (rules is None) == (sample_ids is None):
+            raise ValueError("attention_instances: pass either rules or sample_ids")
+        engine = self._require_engine()
+        if rules is not None:
+            rules = [rules] if isinstance(rules, AI.AttentionRule) else list(rules)
+            ctx = AI.AttentionInstances(engine, AI.resolve_rules(rules, AI.layer_field_names(self)), layer, int(max_instances))
+        else:
+            ids = np.asarray(sample_ids, dtype=np.int64).reshape(-1)
+            n_rows = self._n_rows(x)
+            if ids.size and (ids.min() < 0 or ids.max() >= n_rows):
+                raise ValueError(f"sample_ids outside [0, {n_rows})")
+            ctx = AI.AttentionInstances(engine, None, layer, records=AI.hand_records(ids, engine.H))
+        self._predict_pass(x, batch_size, inst=[ctx], inst_rules=rules, y=y)
+        return ctx.result(y)
+
+    def _n_rows(self, x) -> int:
+        if isinstance(x, np.ndarray) and x.ndim == 2:
+            return x.shape[0]
+        return self._columns(x)[0].shape[0]
+
+    def _attention_pass(self, x, y, domain_ids, batch_size, ctx_ids=None, ctx_rules=None, rules=None):
         from . import attn_stats as AS
         if y is None:
             raise ValueError("attention statistics need the labels: pass y")
@@ -771,7 +839,8 @@ class BaseModel(nn.Module):
         keys = AS.class_keys(domain_ids, y, S, bias)
         engine = self._require_engine()
         ctx = AS.AttentionStatistics(engine, S)
-        pred = self._predict_pass(x, batch_size, ctx, keys)
+        inst = [c for c in (ctx_ids, ctx_rules) if c is not None]
+        pred = self._predict_pass(x, batch_size, ctx, keys, inst=inst, inst_rules=rules, y=y)
         return pred, AS.finish(ctx.raw_sum(), keys, S, bias)
 
     def _column_values(self, x, name) -> np.ndarray:
@@ -789,7 +858,7 @@ class BaseModel(nn.Module):
             at += c.shape[1]
         raise ValueError(f"x has no column for feature {name}")
 
-    def _predict_pass(self, x, batch_size, stats=None, keys=None):
+    def _predict_pass(self, x, batch_size, stats=None, keys=None, inst=(), inst_rules=None, y=None):
         engine = self._require_engine()
         was_training = self.training
         self.eval()
@@ -804,12 +873,26 @@ class BaseModel(nn.Module):
             stream = _os.environ.get("SATRANS_STREAM_INPUT", "0") == "1" or n_rows * n_cols * 4 > (8 << 30)
         out = torch.empty((n_rows, 1), dtype=torch.float32, device=self.device)
         keys_d = torch.from_numpy(keys).to(self.device) if stats is not None else None
+        filtered = inst_rules is not None and any(r.label is not None or r.where for r in inst_rules)
+        y_d = None
+        if filtered and y is not None:
+            if len(y) != n_rows:
+                raise ValueError(f"x has {n_rows} rows, the labels {len(y)}")
+            y_d = torch.as_tensor(np.asarray(y, dtype=np.float64).reshape(-1)).to(self.device)
 
         def run(xb, lo, hi):
-            if stats is None:
+            if stats is None and not inst:
                 return engine.forward(xb, training=False)
-            stats.set_batch(keys_d[lo:hi])
-            return engine.forward(xb, training=False, stats=stats)
+            if stats is not None:
+                stats.set_batch(keys_d[lo:hi])
+            for c in inst:
+                ok = None
+                if c.rules is not None and filtered:      # label and column filters -> rule bits per sample (torch ops)
+                    from . import attn_inst as AI
+                    ok = AI.eligibility(inst_rules, getattr(xb, "ids", xb), None if y_d is None else y_d[lo:hi],
+                                        self.feature_index)
+                c.set_batch(lo, ok)
+            return engine.forward(xb, training=False, stats=stats, inst=inst)
 
         if stream:                                      # host-resident, double-buffered (satrans_amd/pipeline.py)
             from .pipeline import HostBatchFeeder

@@ -568,11 +568,14 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
                 "satrans_bucket_scenarios")
 
     def _run_forward(self, X, ws, training, tabs, att_list=None, rows_ready=False, save_attn=False, n_layers=None,
-                     bucket_ready=False, sorted_io=False, eval_head=False, stats=None) -> bool:
+                     bucket_ready=False, sorted_io=False, eval_head=False, stats=None, inst=()) -> bool:
         """-> True when the head ran too (`eval_head`: the bf16 evaluation stack with the head behind it in the same launch).
         `stats` (attn_stats.AttentionStatistics): every layer writes its attention (into att_list[l], else into the context's one
-        reused buffer) and the statistics kernel is queued right behind it on the same stream."""
+        reused buffer) and the statistics kernel is queued right behind it on the same stream.  `inst` (attn_inst.AttentionInstances
+        contexts): the layers they want write their attention too - into the same buffer, else into the first such context's - and
+        their search is queued behind that layer (behind the statistics).  With either, every layer runs on the fp32 kernels."""
         lib, B, st = self.lib, X.shape[0], self._stream()
+        fwd_bf16 = self.fwd_bf16 and stats is None and not inst
         idt = N.id_dtype_of(X)
         if not bucket_ready:
             self._bucket(X, ws)
@@ -593,7 +596,7 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
         self._stepped_since_forward = False
         # evaluation on the bf16 pipe: the whole stack as ONE launch where it is built (a tile's rows stay in LDS between the
         # layers); `layer_outputs()` then only has the last layer's - callers that want every layer's set engine.bf16_stack = False
-        if self.fwd_bf16 and self.bf16_stack and not training and att_list is None and stats is None and n_layers is None \
+        if fwd_bf16 and self.bf16_stack and not training and att_list is None and n_layers is None \
                 and not ws["generic"] and 1 < self.L <= 4:
             descs = [self._layer_desc(ws, l, B, None, tabs, False, fuse) for l in range(self.L)]
             arr = (C.POINTER(N.LayerDesc) * self.L)(*[C.pointer(d_) for d_ in descs])
@@ -610,22 +613,28 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
         for l in range(self.L if n_layers is None else n_layers):
             desc = self._layer_desc(ws, l, B, None, tabs, training, fuse, attn_save=save_attn, sorted_io=sorted_io)
             att_t = att_list[l] if att_list is not None else (stats.buffer(B) if stats is not None else None)
+            wanted = [c for c in inst if c.wants(l)]
+            if att_t is None and wanted:
+                att_t = wanted[0].buffer(B)
             att = att_t.data_ptr() if att_t is not None else None
             # (layer 0 reads its tokens straight from the embedding arena - the gather fused in: its own phase name, so that what
             #  the random row reads cost shows next to the other layers' time)
             with self.phase("layer_fwd_gather" if (fuse and l == 0 and training) else "layer_fwd"):
-                if ws["generic"] and not (self.fwd_bf16 and not training and att is None
+                if ws["generic"] and not (fwd_bf16 and not training and att is None
                                           and lib.satrans_layer_fwd_bf16_supported(C.byref(desc))):
                     saved = ws["gen_saved"][l if len(ws["gen_saved"]) > l else 0]
                     N.check(lib.satrans_layer_fwd_generic(C.byref(desc), ws["acts"][l + 1].data_ptr(), att, saved.data_ptr(), st),
                             "satrans_layer_fwd_generic")
-                elif self.fwd_bf16 and not training and att is None and lib.satrans_layer_fwd_bf16_supported(C.byref(desc)):
+                elif fwd_bf16 and not training and att is None and lib.satrans_layer_fwd_bf16_supported(C.byref(desc)):
                     N.check(lib.satrans_layer_fwd_bf16(C.byref(desc), ws["acts"][l + 1].data_ptr(), st), "satrans_layer_fwd_bf16")
                 else:
                     N.check(lib.satrans_layer_fwd(C.byref(desc), ws["acts"][l + 1].data_ptr(), att, st), "satrans_layer_fwd")
             if stats is not None:
                 with self.phase("attn_stats"):
                     stats.accumulate(l, att_t, B, st)
+            for c in wanted:
+                with self.phase("attn_inst"):
+                    c.search(l, att_t, X, B, st)
 
     def _pool_gather(self, X, ws, out) -> None:
         """Varlen models: ids -> slot rows [B, R] and - `out` given - the pooled layer input [B, F, D] (csrc/pool.hip)."""
@@ -741,11 +750,14 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
             ws[key] = ok
         return ws[key]
 
-    def forward(self, X: torch.Tensor, training: bool = False, capture_attention: bool = False, stats=None) -> torch.Tensor:
+    def forward(self, X: torch.Tensor, training: bool = False, capture_attention: bool = False, stats=None,
+                inst=()) -> torch.Tensor:
         """Probabilities [B, 1].  `stats` (attn_stats.AttentionStatistics, keys of this batch set): every layer's attention is
         written into one reused [H, B, F, F] buffer and summed per (scenario, label class) into the context's accumulator behind
         that layer.  With it the evaluation runs on the fp32 layer kernels even under set_forward_precision("bf16"): the bf16
-        launches write no attention.  Without it no launch, buffer or code path changes."""
+        launches write no attention.  `inst` (attn_inst.AttentionInstances contexts, their batch set): the instance-level search
+        behind the layer each of them wants, on the same fp32 kernels and - with `stats` - in the same buffer, and the matches'
+        probabilities behind the head.  Without either no launch, buffer or code path changes."""
         self._join_flat()
         self.flush_lazy()
         X = self._prepare_input(X)
@@ -758,8 +770,10 @@ class PathEngine(LocalStepMixin, ReplicatedStepMixin, OwnerStepMixin):
                         for _ in range(self.L)]
         if training:
             self.drop_step += 1
-        if not self._run_forward(X, ws, training, tabs, att_list, eval_head=True, stats=stats):
+        if not self._run_forward(X, ws, training, tabs, att_list, eval_head=True, stats=stats, inst=inst):
             self._head(X, ws)
+        for c in inst:
+            c.finish_batch(ws["prob"], B, self._stream())
         if att_list is not None:
             for layer, att in zip(self.m.domain_int_layers, att_list):
                 layer.normalized_att_scores = att

@@ -93,6 +93,25 @@ class AdamHParams(C.Structure):
                 ("beta2", C.c_float), ("eps", C.c_float), ("l2", C.c_float), ("arith", C.c_int32)]
 
 
+class AttnAtom(C.Structure):
+    """Mirror of `satrans_attn_atom`."""
+    _fields_ = [("q", C.c_int32), ("k", C.c_int32), ("thr", C.c_float)]
+
+
+ATTN_MAX_RULES, ATTN_MAX_CLAUSES, ATTN_MAX_ATOMS, ATTN_MAX_HEADS = 8, 8, 4, 16      # SATRANS_ATTN_MAX_*
+
+
+class AttnRule(C.Structure):
+    """Mirror of `satrans_attn_rule` (a conjunction of clauses, each a disjunction of atoms att[h, b, q, k] > thr)."""
+    _fields_ = [("n_clauses", C.c_int32), ("n_atoms", C.c_int32 * ATTN_MAX_CLAUSES),
+                ("atoms", (AttnAtom * ATTN_MAX_ATOMS) * ATTN_MAX_CLAUSES)]
+
+
+class AttnMatch(C.Structure):
+    """Mirror of `satrans_attn_match` (16 bytes; numpy: ATTN_MATCH_DTYPE in attn_inst.py)."""
+    _fields_ = [("index", C.c_int64), ("head", C.c_int32), ("rule", C.c_int32)]
+
+
 ADAM_EXACT, ADAM_FAST = 0, 1      # satrans_adam_hparams.arith (SATRANS_ADAM_EXACT / SATRANS_ADAM_FAST)
 
 
@@ -200,6 +219,12 @@ SIGNATURES = {
     "satrans_sum_f64": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, _vp]),
     "satrans_attn_stats_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "satrans_attn_stats_accumulate": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_int64, _vp]),
+    "satrans_attn_inst_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "satrans_attn_inst_check_rules": (C.c_int, [C.POINTER(AttnRule), C.c_int, C.c_int]),
+    "satrans_attn_inst_match": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(AttnRule), C.c_int, _vp, C.c_int64, _vp,
+                                          C.c_int64, _vp, _vp, _vp, C.c_int64, _vp]),
+    "satrans_attn_inst_gather": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int64, C.c_int64, _vp, C.c_int64, _vp, _vp,
+                                           _vp, _vp, C.c_int64, C.c_int, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None
