@@ -35,7 +35,8 @@ extern "C" {
 /*    Also in 7, added later: the pooled gather of VarLenSparseFeat fields and its backward (satrans_pool_field,
  *    satrans_pool_gather_fwd, satrans_pool_bwd, satrans_pool_argmax_bytes).  Purely additive - no existing struct or entry point
  *    changed - so a caller built against the earlier version-7 header runs unchanged; the binding checks the new symbols at load.
- *    Likewise the instance-level attention search (satrans_attn_rule, satrans_attn_match, satrans_attn_inst_*). */
+ *    Likewise the instance-level attention search (satrans_attn_rule, satrans_attn_match, satrans_attn_inst_*) and the
+ *    partitioned normalisation (satrans_pnorm_desc, satrans_pnorm_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -346,6 +347,37 @@ int64_t satrans_metanet_scratch_floats(const satrans_metanet_desc* d);
 int satrans_metanet_fwd(const satrans_metanet_desc* d, float* y, float* saved, void* stream);
 int satrans_metanet_bwd(const satrans_metanet_desc* d, const float* dy, float* dx, const float* saved, float* scratch,
                         float* g_tab, float* g_ln, void* stream);
+
+/* Partitioned normalisation = one MDR_BatchNorm per scenario (models/submodules.py:107-175; the loop of star.py:147-154), all
+ * scenarios in one pass:
+ *     y[i] = (x[i] - mean[s]) * invstd[s] * (weight[s] * shared_w) + (bias[s] + shared_b)         s = scenario of row i
+ * x, y, dy, dx [B,C] in the caller's row order; order / seg from satrans_bucket_scenarios; weight, bias, running_mean,
+ * running_var [S,C]; shared_w, shared_b [C].
+ * flags: SATRANS_TRAIN = normalise with the statistics of the batch (mean and biased variance over the scenario's rows) and,
+ *     where running_mean / running_var are given, update them: r = (1 - factor) * r + factor * stat, the unbiased variance
+ *     going into running_var.  Without it the running statistics normalise (both pointers required).
+ * A scenario without rows leaves its running statistics untouched.  A scenario with ONE row has no unbiased variance: torch
+ * refuses it, and so must the caller (the kernels then leave that scenario's running statistics untouched).
+ * saved [2,S,C] = mean, invstd as used by the forward; the backward reads it.  The workspace holds the per-chunk partials of
+ * the two-stage reductions (a chunk = SATRANS_PNORM_ROW_CHUNK rows of one scenario's run); the same buffer may serve both calls.
+ * No floating-point atomics: every merge runs in a fixed order, the result depends on the inputs alone.
+ * The backward WRITES dx, g_weight [S,C], g_bias [S,C], g_shared_w [C], g_shared_b [C] (not accumulated):
+ *     training: dx = (g * invstd / n) * (n * dy - sum(dy) - xhat * sum(dy * xhat)),  g = weight[s] * shared_w,  sums over the scenario
+ *     otherwise: dx = dy * g * invstd */
+#define SATRANS_PNORM_ROW_CHUNK 128
+typedef struct satrans_pnorm_desc {
+    int32_t B, C, S, flags;
+    float eps, factor;
+    const float* x;
+    const int32_t *order, *seg;
+    const float *weight, *bias, *shared_w, *shared_b;
+    float *running_mean, *running_var;
+} satrans_pnorm_desc;
+int64_t satrans_pnorm_saved_floats(const satrans_pnorm_desc* d);
+int64_t satrans_pnorm_workspace_floats(const satrans_pnorm_desc* d);
+int satrans_pnorm_fwd(const satrans_pnorm_desc* d, float* y, float* saved, float* workspace, void* stream);
+int satrans_pnorm_bwd(const satrans_pnorm_desc* d, const float* dy, float* dx, const float* saved, float* workspace,
+                      float* g_weight, float* g_bias, float* g_shared_w, float* g_shared_b, void* stream);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

@@ -7,7 +7,11 @@
     (models/submodules.py:64-103): the scenario embedding, the one-Linear scenario encoder and the MetaNet over the embedding
     block.  The generated weights are tabulated per SCENARIO ([S,P], S rows) instead of per sample ([B,P]).
 
-Both are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip) wrapped in a
+  * `MDR_BatchNorm` - reference models/submodules.py:107-175, the partitioned normalisation of STAR (`use_domain_bn` in
+    models/star.py:81-82,147-154): same constructor, parameters, buffers and state_dict keys; and `PartitionedNorm`, the
+    ModuleList of them that star.py loops over, as ONE pass over all scenarios (csrc/pnorm.hip).
+
+All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip) wrapped in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -16,6 +20,7 @@ import ctypes as C
 
 import torch
 import torch.nn as nn
+from torch.nn.modules.batchnorm import _NormBase
 
 from . import native as N
 
@@ -192,3 +197,180 @@ class MetaTransformation(nn.Module):
         w = self.ffn_layer_norm.weight if self.use_norm else None
         b = self.ffn_layer_norm.bias if self.use_norm else None
         return _MetaNetFn.apply(fm_input, table, w, b, scenario_ids.reshape(-1), self)
+
+
+class _PNormFn(torch.autograd.Function):
+    """y = BN_{scenario(i)}(x[i]) for all scenarios at once (csrc/pnorm.hip).  weight, bias [S,C]; running_mean, running_var [S,C]
+    or None, updated in place when `batch_stats` (the kernels leave a scenario without rows untouched)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, shared_w, shared_b, order, seg, running_mean, running_var, factor, eps, batch_stats):
+        lib = N.lib()
+        dev = x.device
+        x, weight, bias = x.contiguous(), weight.contiguous(), bias.contiguous()
+        shared_w, shared_b = shared_w.contiguous(), shared_b.contiguous()
+        d = _pnorm_desc(x, weight, bias, shared_w, shared_b, order, seg, running_mean, running_var, factor, eps, batch_stats)
+        saved = torch.empty(_pnorm_size(lib.satrans_pnorm_saved_floats, d), dtype=torch.float32, device=dev)
+        work = torch.empty(_pnorm_size(lib.satrans_pnorm_workspace_floats, d), dtype=torch.float32, device=dev)
+        y = torch.empty_like(x)
+        N.check(lib.satrans_pnorm_fwd(C.byref(d), y.data_ptr(), saved.data_ptr(), work.data_ptr(), N.stream_handle(dev)),
+                "satrans_pnorm_fwd")
+        ctx.args = (factor, eps, batch_stats)
+        ctx.save_for_backward(x, weight, bias, shared_w, shared_b, order, seg, saved)
+        ctx.mark_non_differentiable(saved)
+        return y, saved
+
+    @staticmethod
+    def backward(ctx, dy, _dsaved):
+        lib = N.lib()
+        x, weight, bias, shared_w, shared_b, order, seg, saved = ctx.saved_tensors
+        d = _pnorm_desc(x, weight, bias, shared_w, shared_b, order, seg, None, None, *ctx.args)
+        work = torch.empty(_pnorm_size(lib.satrans_pnorm_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx, g_w, g_b = torch.empty_like(x), torch.empty_like(weight), torch.empty_like(bias)
+        g_sw, g_sb = torch.empty_like(shared_w), torch.empty_like(shared_b)
+        N.check(lib.satrans_pnorm_bwd(C.byref(d), dy.contiguous().data_ptr(), dx.data_ptr(), saved.data_ptr(), work.data_ptr(),
+                                      g_w.data_ptr(), g_b.data_ptr(), g_sw.data_ptr(), g_sb.data_ptr(), N.stream_handle(x.device)),
+                "satrans_pnorm_bwd")
+        return dx, g_w, g_b, g_sw, g_sb, None, None, None, None, None, None, None
+
+
+def _pnorm_desc(x, weight, bias, shared_w, shared_b, order, seg, running_mean, running_var, factor, eps, batch_stats):
+    d = N.PNormDesc()
+    d.B, d.C, d.S = x.shape[0], x.shape[1], weight.shape[0]
+    d.flags, d.eps, d.factor = (N.TRAIN if batch_stats else 0), eps, factor
+    d.x, d.order, d.seg = x.data_ptr(), order.data_ptr(), seg.data_ptr()
+    d.weight, d.bias, d.shared_w, d.shared_b = weight.data_ptr(), bias.data_ptr(), shared_w.data_ptr(), shared_b.data_ptr()
+    d.running_mean = running_mean.data_ptr() if running_mean is not None else None
+    d.running_var = running_var.data_ptr() if running_var is not None else None
+    return d
+
+
+def _pnorm_size(fn, d):
+    n = int(fn(C.byref(d)))
+    if n < 0:
+        N.check(n, fn.__name__)
+    return n
+
+
+def _pnorm_check_input(x, shared_weight, shared_bias, num_features, what):
+    if x.dim() == 3:
+        raise NotImplementedError(f"{what}: 3-D input is not built; pass the 2-D form [n, C] (the reference's only caller does)")
+    if x.dim() != 2:
+        raise ValueError("expected 2D or 3D input (got {}D input)".format(x.dim()))
+    N.require_gpu(x, what)
+    if x.dtype != torch.float32 or shared_weight.dtype != torch.float32 or shared_bias.dtype != torch.float32:
+        raise TypeError(f"{what}: rows, parameters and gradients are float32")
+    if x.shape[1] != num_features or shared_weight.numel() != num_features or shared_bias.numel() != num_features:
+        raise ValueError(f"{what}: expected {num_features} channels, got input {tuple(x.shape)}, shared weight "
+                         f"{tuple(shared_weight.shape)}, shared bias {tuple(shared_bias.shape)}")
+
+
+def _pnorm_run(bns, x, order, seg, counts, shared_weight, shared_bias, training):
+    """The reference's MDR_BatchNorm.forward for every module of `bns` at once (module s owns the rows of scenario s; `counts` are
+    the host-side row counts).  Every check runs before the first buffer is written.  -> y, [2,S,C] = the mean and
+    1 / sqrt(var + eps) the forward normalised with (the modules keep it as `last_stats`)."""
+    first = bns[0]
+    tracked = first.track_running_stats
+    batch_stats = training or not tracked                 # reference: training, or evaluation without buffers
+    if batch_stats and 1 in counts:                       # torch.nn.functional._verify_batch_size
+        raise ValueError("Expected more than 1 value per channel when training, got input size {}".format(
+            torch.Size([1, x.shape[1]])))
+    factor = 0.0 if first.momentum is None else float(first.momentum)
+    update = training and tracked
+    if update and first.momentum is None:                 # cumulative average: 1 / num_batches_tracked, after its increment
+        seen = set(torch.stack([m.num_batches_tracked for m in bns]).tolist())
+        if len(seen) != 1:
+            raise NotImplementedError("momentum=None with num_batches_tracked differing between the scenarios' modules")
+        factor = 1.0 / float(seen.pop() + 1)
+    if update:
+        torch._foreach_add_([m.num_batches_tracked for m in bns], 1)
+    running_mean = running_var = None
+    if tracked:
+        running_mean = torch.stack([m.running_mean for m in bns])
+        running_var = torch.stack([m.running_var for m in bns])
+    weight, bias = torch.stack([m.weight for m in bns]), torch.stack([m.bias for m in bns])
+    y, saved = _PNormFn.apply(x, weight, bias, shared_weight.reshape(-1), shared_bias.reshape(-1), order, seg, running_mean,
+                          running_var, factor, float(first.eps), batch_stats)
+    if update:
+        with torch.no_grad():
+            torch._foreach_copy_([m.running_mean for m in bns] + [m.running_var for m in bns],
+                                 list(running_mean.unbind(0)) + list(running_var.unbind(0)))
+    return y, saved.view(2, len(bns), -1)
+
+
+class MDR_BatchNorm(_NormBase):
+    """One scenario's batch-norm whose scale and shift are multiplied / added onto a shared pair:
+    F.batch_norm(input, running_mean, running_var, weight * shared_weight, bias + shared_bias, ...).  Parameters, buffers,
+    state_dict keys, the momentum=None rule (cumulative average, factor 1 / num_batches_tracked) and the rule for when batch
+    statistics are used are the reference's.  affine=False is refused at construction (the reference's forward would compute
+    None * tensor); 3-D input is not built.  Internally the one-scenario case of PartitionedNorm's launches."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1, affine=True, track_running_stats=True, device=None, dtype=None):
+        if not affine:
+            raise ValueError("MDR_BatchNorm needs affine=True: its forward multiplies weight by the shared weight")
+        if dtype not in (None, torch.float32):
+            raise TypeError("MDR_BatchNorm: parameters are float32")
+        super().__init__(num_features, eps, momentum, affine, track_running_stats, device=device, dtype=dtype)
+        self.last_stats = None
+
+    def _check_input_dim(self, input):
+        if input.dim() != 2 and input.dim() != 3:
+            raise ValueError("expected 2D or 3D input (got {}D input)".format(input.dim()))
+
+    def forward(self, input, shared_weight, shared_bias):
+        _pnorm_check_input(input, shared_weight, shared_bias, self.num_features, "MDR_BatchNorm")
+        n = input.shape[0]
+        if n == 0:      # torch: an empty input passes through, the running statistics stay, the batch is counted
+            if self.training and self.track_running_stats:
+                self.num_batches_tracked.add_(1)
+            return input * (self.weight * shared_weight) + (self.bias + shared_bias)
+        order = torch.arange(n, dtype=torch.int32, device=input.device)
+        seg = torch.tensor([0, n], dtype=torch.int32, device=input.device)
+        y, self.last_stats = _pnorm_run([self], input, order, seg, [n], shared_weight, shared_bias, self.training)
+        return y
+
+
+class PartitionedNorm(nn.Module):
+    """STAR's partitioned normalisation: `bns = ModuleList(MDR_BatchNorm(num_features) for each scenario)` (state_dict keys
+    `bns.{i}.*`, as in the reference's Star_Net) applied to a mixed batch in one pass.  Replaces the loop of models/star.py:147-154
+
+        for i in range(num_domains):
+            rows = x[domain_ids == i + domain_id_offset]
+            out[domain_ids == i + domain_id_offset] = bns[i](rows, shared_weight, shared_bias)
+
+    by: bucket the ids (satrans_bucket_scenarios), one forward over all scenarios, every module's num_batches_tracked
+    incremented as the loop does (a scenario without rows keeps its running statistics, as torch does for an empty input).
+
+    Differences from the loop.  (1) A scenario with exactly ONE row in training mode raises torch's ValueError("Expected more
+    than 1 value per channel when training, ...") BEFORE any buffer is written; in the loop the scenarios in front of the
+    offending one would already have updated theirs.  (2) An id outside [offset, offset + num_domains) raises IndexError; the
+    loop silently leaves such rows out.  One device-to-host read per forward (the S + 1 segment bounds) serves both checks."""
+
+    def __init__(self, num_features, num_domains, eps=1e-5, momentum=0.1):
+        super().__init__()
+        if num_domains < 1:
+            raise ValueError("num_domains must be >= 1")
+        self.num_features, self.num_domains = num_features, num_domains
+        self.bns = nn.ModuleList([MDR_BatchNorm(num_features, eps=eps, momentum=momentum) for _ in range(num_domains)])
+        self.last_stats = None
+
+    def forward(self, x, domain_ids, shared_weight, shared_bias, domain_id_offset=0):
+        _pnorm_check_input(x, shared_weight, shared_bias, self.num_features, "PartitionedNorm")
+        lib = N.lib()
+        B, S, dev = x.shape[0], self.num_domains, x.device
+        if B == 0 or domain_ids.numel() != B:
+            raise ValueError(f"PartitionedNorm: {B} rows with {domain_ids.numel()} scenario ids")
+        i32 = dict(dtype=torch.int32, device=dev)
+        sid_in = (domain_ids.reshape(-1).to(device=dev, dtype=torch.int64) - int(domain_id_offset)).to(torch.int32).contiguous()
+        sid, order, seg = torch.empty(B, **i32), torch.empty(B, **i32), torch.empty(S + 1, **i32)
+        status = torch.zeros(1, **i32)
+        bucket = torch.empty(int(lib.satrans_bucket_workspace_bytes(B, S)), dtype=torch.uint8, device=dev)
+        N.check(lib.satrans_bucket_scenarios(sid_in.data_ptr(), N.ID_I32, 1, 0, B, S, sid.data_ptr(), order.data_ptr(), seg.data_ptr(),
+                                             status.data_ptr(), bucket.data_ptr(), bucket.numel(), N.stream_handle(dev)),
+                "satrans_bucket_scenarios")
+        host = torch.cat([seg, status]).tolist()
+        if host[-1] != 0:
+            raise IndexError(f"PartitionedNorm: a scenario id lies outside [{domain_id_offset}, {domain_id_offset + S})")
+        counts = [host[s + 1] - host[s] for s in range(S)]
+        y, self.last_stats = _pnorm_run(list(self.bns), x, order, seg, counts, shared_weight, shared_bias, self.training)
+        return y

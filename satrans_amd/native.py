@@ -76,6 +76,16 @@ class MetaNetDesc(C.Structure):
                 ("tab_stride", C.c_int64), ("x", _vp), ("order", _vp), ("seg", _vp), ("tab", _vp), ("ln_g", _vp), ("ln_b", _vp)]
 
 
+class PNormDesc(C.Structure):
+    """Mirror of `satrans_pnorm_desc`."""
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("S", C.c_int32), ("flags", C.c_int32), ("eps", C.c_float), ("factor", C.c_float),
+                ("x", _vp), ("order", _vp), ("seg", _vp), ("weight", _vp), ("bias", _vp), ("shared_w", _vp), ("shared_b", _vp),
+                ("running_mean", _vp), ("running_var", _vp)]
+
+
+PNORM_ROW_CHUNK = 128      # SATRANS_PNORM_ROW_CHUNK: rows of one scenario's run that a workgroup of the reductions takes
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -158,6 +168,10 @@ SIGNATURES = {
     "satrans_metanet_scratch_floats": (C.c_int64, [C.POINTER(MetaNetDesc)]),
     "satrans_metanet_fwd": (C.c_int, [C.POINTER(MetaNetDesc), _vp, _vp, _vp]),
     "satrans_metanet_bwd": (C.c_int, [C.POINTER(MetaNetDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "satrans_pnorm_saved_floats": (C.c_int64, [C.POINTER(PNormDesc)]),
+    "satrans_pnorm_workspace_floats": (C.c_int64, [C.POINTER(PNormDesc)]),
+    "satrans_pnorm_fwd": (C.c_int, [C.POINTER(PNormDesc), _vp, _vp, _vp, _vp]),
+    "satrans_pnorm_bwd": (C.c_int, [C.POINTER(PNormDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
