@@ -36,7 +36,8 @@ extern "C" {
  *    satrans_pool_gather_fwd, satrans_pool_bwd, satrans_pool_argmax_bytes).  Purely additive - no existing struct or entry point
  *    changed - so a caller built against the earlier version-7 header runs unchanged; the binding checks the new symbols at load.
  *    Likewise the instance-level attention search (satrans_attn_rule, satrans_attn_match, satrans_attn_inst_*) and the
- *    partitioned normalisation (satrans_pnorm_desc, satrans_pnorm_*). */
+ *    partitioned normalisation (satrans_pnorm_desc, satrans_pnorm_*), and after it STAR's star-topology towers
+ *    (satrans_star_desc, satrans_star_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -378,6 +379,44 @@ int64_t satrans_pnorm_workspace_floats(const satrans_pnorm_desc* d);
 int satrans_pnorm_fwd(const satrans_pnorm_desc* d, float* y, float* saved, float* workspace, void* stream);
 int satrans_pnorm_bwd(const satrans_pnorm_desc* d, const float* dy, float* dx, const float* saved, float* workspace,
                       float* g_weight, float* g_bias, float* g_shared_w, float* g_shared_b, void* stream);
+
+/* STAR's star-topology towers (models/star.py:156-170) for a mixed batch.  Layer l = 0 .. L-1 maps width n_{l-1} to n_l = width[l]
+ * (n_{-1} = C; the last layer is the logit, width[L-1] == 1); row i belongs to scenario s:
+ *     W_eff[s,l] = w_dom[l][s] * w_sh[l]   (elementwise, [n_l, n_{l-1}])        b_eff[s,l] = b_dom[l][s] + b_sh[l]
+ *     h_l[i] = relu(h_{l-1}[i] W_eff[s,l]^T + b_eff[s,l])   for l < L-1,        logit[i] = h_{L-2}[i] W_eff[s,L-1]^T + b_eff[s,L-1]
+ * x [B,C], logit / dlogit [B] and dx [B,C] in the caller's row order; order / seg from satrans_bucket_scenarios;
+ * w_dom[l] [S, n_l, n_{l-1}], b_dom[l] [S, n_l] (the scenarios' parameters stacked), w_sh[l] [n_l, n_{l-1}], b_sh[l] [n_l].
+ * fp32 throughout, products on the exact f32-input MFMA.  C and the widths are any positive integers; 1 to 4 hidden layers.
+ * saved = the hidden rows h_0 .. h_{L-2}, [B, n_l] each, layer after layer, in the caller's row order: B * sum of the hidden
+ * widths floats; the backward reads them (nothing is recomputed).  The forward needs no workspace; the backward's holds two
+ * [B, widest hidden layer] buffers for dz and the per-chunk partials of the weight gradients of the layer in hand
+ * (a chunk = SATRANS_STAR_DW_ROW_CHUNK rows counted from the start of a scenario's run):
+ *     2 * B * max hidden width + (ceil(B / SATRANS_STAR_DW_ROW_CHUNK) + S) * max over l of n_l * (n_{l-1} + 1)   floats.
+ * The backward WRITES (does not accumulate) dx and, per layer, g_w_dom[l] [S, n_l, n_{l-1}], g_b_dom[l] [S, n_l],
+ * g_w_sh[l] [n_l, n_{l-1}], g_b_sh[l] [n_l] (arrays of L pointers):
+ *     dz_l = dh_l * (h_l > 0)  (dz_{L-1} = dlogit),   dh_{l-1} = dz_l W_eff[s,l],   dW_eff[s,l] = dz_l^T h_{l-1} over the scenario's rows,
+ *     g_w_dom = dW_eff * w_sh,  g_b_dom = column sums of dz_l,  g_w_sh = sum over s of dW_eff[s] * w_dom[s],  g_b_sh = sum over s of g_b_dom[s].
+ * No floating-point atomics: chunks merge in chunk order, scenarios in scenario order, so equal inputs give equal bits and a
+ * scenario's rows give the same bits alone as inside a mixed batch.  A scenario without rows gets zeros in its gradients. */
+#define SATRANS_STAR_ROW_TILE 64
+#define SATRANS_STAR_DW_ROW_CHUNK 256
+#define SATRANS_STAR_MAX_LAYERS 5
+typedef struct satrans_star_desc {
+    int32_t B, C, S, L;
+    int32_t width[SATRANS_STAR_MAX_LAYERS];
+    int32_t reserved;      /* 0 */
+    const float* x;
+    const int32_t *order, *seg;
+    const float* w_dom[SATRANS_STAR_MAX_LAYERS];
+    const float* b_dom[SATRANS_STAR_MAX_LAYERS];
+    const float* w_sh[SATRANS_STAR_MAX_LAYERS];
+    const float* b_sh[SATRANS_STAR_MAX_LAYERS];
+} satrans_star_desc;
+int64_t satrans_star_saved_floats(const satrans_star_desc* d);
+int64_t satrans_star_workspace_floats(const satrans_star_desc* d);
+int satrans_star_fwd(const satrans_star_desc* d, float* logit, float* saved, void* stream);
+int satrans_star_bwd(const satrans_star_desc* d, const float* dlogit, float* dx, const float* saved, float* workspace,
+                     float* const* g_w_dom, float* const* g_b_dom, float* const* g_w_sh, float* const* g_b_sh, void* stream);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

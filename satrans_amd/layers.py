@@ -11,7 +11,11 @@
     models/star.py:81-82,147-154): same constructor, parameters, buffers and state_dict keys; and `PartitionedNorm`, the
     ModuleList of them that star.py loops over, as ONE pass over all scenarios (csrc/pnorm.hip).
 
-All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip) wrapped in a
+  * `StarTowers` - STAR's star-topology FC towers (models/star.py:156-170: per-scenario weight * shared weight, applied to each
+    scenario's rows) for a mixed batch (csrc/star.hip), and `StarHead`, the scenario-dependent half of `Star_Net.forward`
+    (star.py:144-173): the partitioned normalisation, then the towers, on one bucketing of the batch.
+
+All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip) wrapped in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -298,6 +302,28 @@ def _pnorm_run(bns, x, order, seg, counts, shared_weight, shared_bias, training)
     return y, saved.view(2, len(bns), -1)
 
 
+def _bucket_rows(x, domain_ids, S, domain_id_offset, what):
+    """Bucket the rows of x by scenario id - offset (satrans_bucket_scenarios) -> order [B], seg [S+1] on the device and the
+    host-side row counts.  One device-to-host read (the S + 1 segment bounds and the status word); an id outside
+    [offset, offset + S) raises IndexError."""
+    lib = N.lib()
+    B, dev = x.shape[0], x.device
+    if B == 0 or domain_ids.numel() != B:
+        raise ValueError(f"{what}: {B} rows with {domain_ids.numel()} scenario ids")
+    i32 = dict(dtype=torch.int32, device=dev)
+    sid_in = (domain_ids.reshape(-1).to(device=dev, dtype=torch.int64) - int(domain_id_offset)).to(torch.int32).contiguous()
+    sid, order, seg = torch.empty(B, **i32), torch.empty(B, **i32), torch.empty(S + 1, **i32)
+    status = torch.zeros(1, **i32)
+    bucket = torch.empty(int(lib.satrans_bucket_workspace_bytes(B, S)), dtype=torch.uint8, device=dev)
+    N.check(lib.satrans_bucket_scenarios(sid_in.data_ptr(), N.ID_I32, 1, 0, B, S, sid.data_ptr(), order.data_ptr(), seg.data_ptr(),
+                                         status.data_ptr(), bucket.data_ptr(), bucket.numel(), N.stream_handle(dev)),
+            "satrans_bucket_scenarios")
+    host = torch.cat([seg, status]).tolist()
+    if host[-1] != 0:
+        raise IndexError(f"{what}: a scenario id lies outside [{domain_id_offset}, {domain_id_offset + S})")
+    return order, seg, [host[s + 1] - host[s] for s in range(S)]
+
+
 class MDR_BatchNorm(_NormBase):
     """One scenario's batch-norm whose scale and shift are multiplied / added onto a shared pair:
     F.batch_norm(input, running_mean, running_var, weight * shared_weight, bias + shared_bias, ...).  Parameters, buffers,
@@ -356,21 +382,167 @@ class PartitionedNorm(nn.Module):
 
     def forward(self, x, domain_ids, shared_weight, shared_bias, domain_id_offset=0):
         _pnorm_check_input(x, shared_weight, shared_bias, self.num_features, "PartitionedNorm")
-        lib = N.lib()
-        B, S, dev = x.shape[0], self.num_domains, x.device
-        if B == 0 or domain_ids.numel() != B:
-            raise ValueError(f"PartitionedNorm: {B} rows with {domain_ids.numel()} scenario ids")
-        i32 = dict(dtype=torch.int32, device=dev)
-        sid_in = (domain_ids.reshape(-1).to(device=dev, dtype=torch.int64) - int(domain_id_offset)).to(torch.int32).contiguous()
-        sid, order, seg = torch.empty(B, **i32), torch.empty(B, **i32), torch.empty(S + 1, **i32)
-        status = torch.zeros(1, **i32)
-        bucket = torch.empty(int(lib.satrans_bucket_workspace_bytes(B, S)), dtype=torch.uint8, device=dev)
-        N.check(lib.satrans_bucket_scenarios(sid_in.data_ptr(), N.ID_I32, 1, 0, B, S, sid.data_ptr(), order.data_ptr(), seg.data_ptr(),
-                                             status.data_ptr(), bucket.data_ptr(), bucket.numel(), N.stream_handle(dev)),
-                "satrans_bucket_scenarios")
-        host = torch.cat([seg, status]).tolist()
-        if host[-1] != 0:
-            raise IndexError(f"PartitionedNorm: a scenario id lies outside [{domain_id_offset}, {domain_id_offset + S})")
-        counts = [host[s + 1] - host[s] for s in range(S)]
+        order, seg, counts = _bucket_rows(x, domain_ids, self.num_domains, domain_id_offset, "PartitionedNorm")
         y, self.last_stats = _pnorm_run(list(self.bns), x, order, seg, counts, shared_weight, shared_bias, self.training)
         return y
+
+
+class _StarFn(torch.autograd.Function):
+    """logit [B,1] of the towers for all scenarios at once (csrc/star.hip).  `tensors` = L stacked per-scenario weights
+    [S, n_l, n_{l-1}], L stacked biases [S, n_l], L shared weights, L shared biases."""
+
+    @staticmethod
+    def forward(ctx, x, order, seg, L, *tensors):
+        lib = N.lib()
+        dev = x.device
+        x = x.contiguous()
+        tensors = tuple(t.contiguous() for t in tensors)
+        d = _star_desc(x, order, seg, L, tensors)
+        saved = torch.empty(_pnorm_size(lib.satrans_star_saved_floats, d), dtype=torch.float32, device=dev)
+        logit = torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev)
+        N.check(lib.satrans_star_fwd(C.byref(d), logit.data_ptr(), saved.data_ptr(), N.stream_handle(dev)), "satrans_star_fwd")
+        ctx.L = L
+        ctx.save_for_backward(x, order, seg, saved, *tensors)
+        ctx.mark_non_differentiable(saved)
+        return logit, saved
+
+    @staticmethod
+    def backward(ctx, dlogit, _dsaved):
+        lib = N.lib()
+        x, order, seg, saved, *tensors = ctx.saved_tensors
+        L = ctx.L
+        d = _star_desc(x, order, seg, L, tensors)
+        work = torch.empty(_pnorm_size(lib.satrans_star_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        grads = [torch.empty_like(t) for t in tensors]
+        groups = [(C.c_void_p * L)(*[g.data_ptr() for g in grads[k * L:(k + 1) * L]]) for k in range(4)]
+        N.check(lib.satrans_star_bwd(C.byref(d), dlogit.contiguous().data_ptr(), dx.data_ptr(), saved.data_ptr(), work.data_ptr(),
+                                     groups[0], groups[1], groups[2], groups[3], N.stream_handle(x.device)), "satrans_star_bwd")
+        return (dx, None, None, None, *grads)
+
+
+def _star_desc(x, order, seg, L, tensors):
+    d = N.StarDesc()
+    d.B, d.C, d.S, d.L = x.shape[0], x.shape[1], tensors[0].shape[0], L
+    d.x, d.order, d.seg = x.data_ptr(), order.data_ptr(), seg.data_ptr()
+    for l in range(L):
+        d.width[l] = tensors[l].shape[1]
+        d.w_dom[l], d.b_dom[l] = tensors[l].data_ptr(), tensors[L + l].data_ptr()
+        d.w_sh[l], d.b_sh[l] = tensors[2 * L + l].data_ptr(), tensors[3 * L + l].data_ptr()
+    return d
+
+
+class _TowerDNN(nn.Module):
+    """The Linear layers of the reference's DNN (state_dict keys `linears.{l}.{weight,bias}`); relu, no dropout, no batch-norm.
+    A holder of parameters: the towers' arithmetic runs in csrc/star.hip."""
+
+    def __init__(self, inputs_dim, hidden_units, init_std):
+        super().__init__()
+        units = [inputs_dim] + list(hidden_units)
+        self.linears = nn.ModuleList([nn.Linear(units[i], units[i + 1]) for i in range(len(units) - 1)])
+        for lin in self.linears:
+            nn.init.normal_(lin.weight, mean=0, std=init_std)
+
+
+class StarTowers(nn.Module):
+    """STAR's star-topology FC towers over a mixed batch: scenario s applies, layer by layer,
+
+        relu(F.linear(h, domain_dnns[s].linears[l].weight * shared_dnn.linears[l].weight,
+                         domain_dnns[s].linears[l].bias + shared_dnn.linears[l].bias))
+
+    and at the end F.linear(h, domain_dnn_linears[s].weight * shared_dnn_linear.weight, the two biases summed) to the rows
+    whose id is s + domain_id_offset - the loop of models/star.py:147-170 without its normalisation.  Parameter names, shapes
+    and initialisation are the reference Star_Net's (weights of the towers N(0, init_std); biases and the final nn.Linears
+    torch's default), so the tower entries of a reference checkpoint load with load_state_dict.
+
+    forward(x [B, inputs_dim] fp32, domain_ids [B], domain_id_offset=0) -> logit [B,1]; the caller applies the sigmoid.
+    Per call: the per-scenario parameters are stacked (torch.stack; autograd splits the gradients back), the ids bucketed
+    (one device-to-host read), and one autograd.Function runs satrans_star_fwd / satrans_star_bwd.  `last_hidden` holds the
+    hidden rows of the last forward, [B, n_l] per hidden layer.
+
+    Differences from the loop.  An id outside [offset, offset + num_domains) raises IndexError; the loop silently leaves such
+    rows at logit 0.  Not built (main.py passes none of them): an activation other than relu, dropout, batch-norm inside the
+    towers - NotImplementedError at construction.  1 to 4 hidden layers of any positive width."""
+
+    def __init__(self, inputs_dim, hidden_units=(256, 128), num_domains=1, init_std=0.0001, activation='relu', dropout_rate=0,
+                 use_bn=False):
+        super().__init__()
+        self._build_towers(inputs_dim, hidden_units, num_domains, init_std, activation, dropout_rate, use_bn)
+
+    def _build_towers(self, inputs_dim, hidden_units, num_domains, init_std, activation, dropout_rate, use_bn):
+        if activation != 'relu':
+            raise NotImplementedError(f"StarTowers: activation {activation!r} is not built (relu only)")
+        if dropout_rate != 0:
+            raise NotImplementedError("StarTowers: dropout inside the towers is not built (dropout_rate must be 0)")
+        if use_bn:
+            raise NotImplementedError("StarTowers: batch-norm inside the towers is not built (use_bn must be False)")
+        hidden_units = [int(u) for u in hidden_units]
+        if not 1 <= len(hidden_units) <= N.STAR_MAX_LAYERS - 1:
+            raise NotImplementedError(f"StarTowers: 1 to {N.STAR_MAX_LAYERS - 1} hidden layers, got {len(hidden_units)}")
+        if inputs_dim < 1 or min(hidden_units) < 1 or num_domains < 1:
+            raise ValueError("StarTowers: inputs_dim, hidden_units and num_domains must be positive")
+        self.inputs_dim, self.hidden_units, self.num_domains = int(inputs_dim), tuple(hidden_units), int(num_domains)
+        self.domain_dnns = nn.ModuleList([_TowerDNN(inputs_dim, hidden_units, init_std) for _ in range(num_domains)])
+        self.domain_dnn_linears = nn.ModuleList([nn.Linear(hidden_units[-1], 1) for _ in range(num_domains)])
+        self.shared_dnn = _TowerDNN(inputs_dim, hidden_units, init_std)
+        self.shared_dnn_linear = nn.Linear(hidden_units[-1], 1)
+        self.last_hidden = None
+
+    def _check_input(self, x, what):
+        if x.dim() != 2 or x.shape[1] != self.inputs_dim:
+            raise ValueError(f"{what}: expected input [B, {self.inputs_dim}], got {tuple(x.shape)}")
+        N.require_gpu(x, what)
+        if x.dtype != torch.float32 or self.shared_dnn_linear.weight.dtype != torch.float32:
+            raise TypeError(f"{what}: rows, parameters and gradients are float32")
+
+    def _run_towers(self, x, order, seg):
+        S, H = self.num_domains, len(self.hidden_units)
+        doms = [[self.domain_dnns[s].linears[l] for s in range(S)] for l in range(H)] + [list(self.domain_dnn_linears)]
+        shared = list(self.shared_dnn.linears) + [self.shared_dnn_linear]
+        tensors = ([torch.stack([m.weight for m in layer]) for layer in doms] + [torch.stack([m.bias for m in layer]) for layer in doms]
+                   + [m.weight for m in shared] + [m.bias for m in shared])
+        logit, saved = _StarFn.apply(x, order, seg, H + 1, *tensors)
+        B, at, self.last_hidden = x.shape[0], 0, []
+        for n in self.hidden_units:
+            self.last_hidden.append(saved[at:at + B * n].view(B, n))
+            at += B * n
+        return logit
+
+    def forward(self, x, domain_ids, domain_id_offset=0):
+        self._check_input(x, "StarTowers")
+        order, seg, _ = _bucket_rows(x, domain_ids, self.num_domains, domain_id_offset, "StarTowers")
+        return self._run_towers(x, order, seg)
+
+
+class StarHead(StarTowers):
+    """The scenario-dependent half of the reference's Star_Net.forward (models/star.py:144-173) as one module: the partitioned
+    normalisation (when use_domain_bn), then the star-topology towers, on ONE bucketing of the batch.  Owns, under the
+    reference's top-level names, shared_bn_weight, shared_bn_bias, bns.{s}.* (MDR_BatchNorm; only with use_domain_bn) and the
+    four tower groups of StarTowers, in the reference's creation order.
+
+    forward(dnn_input [B, inputs_dim], domain_ids [B], domain_id_offset=0) -> logit [B,1]; the caller applies the sigmoid.
+    PartitionedNorm's differences from the loop hold here too: a scenario with exactly one row in training mode raises torch's
+    ValueError before any buffer is written, an id out of range raises IndexError.  Without use_domain_bn the shared
+    normalisation parameters exist and stay unused, as in the reference."""
+
+    def __init__(self, inputs_dim, hidden_units=(256, 128), num_domains=1, use_domain_bn=True, init_std=0.0001, activation='relu',
+                 dropout_rate=0, use_bn=False, eps=1e-5, momentum=0.1):
+        nn.Module.__init__(self)
+        self.use_domain_bn = bool(use_domain_bn)
+        self.shared_bn_weight = nn.Parameter(torch.ones(inputs_dim))
+        self.shared_bn_bias = nn.Parameter(torch.zeros(inputs_dim))
+        if self.use_domain_bn:
+            self.bns = nn.ModuleList([MDR_BatchNorm(inputs_dim, eps=eps, momentum=momentum) for _ in range(num_domains)])
+        self._build_towers(inputs_dim, hidden_units, num_domains, init_std, activation, dropout_rate, use_bn)
+        self.last_stats = None
+
+    def forward(self, dnn_input, domain_ids, domain_id_offset=0):
+        self._check_input(dnn_input, "StarHead")
+        if self.use_domain_bn:
+            _pnorm_check_input(dnn_input, self.shared_bn_weight, self.shared_bn_bias, self.inputs_dim, "StarHead")
+        order, seg, counts = _bucket_rows(dnn_input, domain_ids, self.num_domains, domain_id_offset, "StarHead")
+        h = dnn_input
+        if self.use_domain_bn:
+            h, self.last_stats = _pnorm_run(list(self.bns), h, order, seg, counts, self.shared_bn_weight, self.shared_bn_bias,
+                                            self.training)
+        return self._run_towers(h, order, seg)

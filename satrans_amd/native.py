@@ -86,6 +86,19 @@ class PNormDesc(C.Structure):
 PNORM_ROW_CHUNK = 128      # SATRANS_PNORM_ROW_CHUNK: rows of one scenario's run that a workgroup of the reductions takes
 
 
+STAR_ROW_TILE = 64           # SATRANS_STAR_ROW_TILE: rows of one scenario's run under a workgroup of the tower products
+STAR_DW_ROW_CHUNK = 256      # SATRANS_STAR_DW_ROW_CHUNK: rows of a run that one partial of the weight gradients sums
+STAR_MAX_LAYERS = 5          # SATRANS_STAR_MAX_LAYERS: up to 4 hidden layers and the logit layer
+
+
+class StarDesc(C.Structure):
+    """Mirror of `satrans_star_desc`."""
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("S", C.c_int32), ("L", C.c_int32), ("width", C.c_int32 * STAR_MAX_LAYERS),
+                ("reserved", C.c_int32), ("x", _vp), ("order", _vp), ("seg", _vp),
+                ("w_dom", _vp * STAR_MAX_LAYERS), ("b_dom", _vp * STAR_MAX_LAYERS), ("w_sh", _vp * STAR_MAX_LAYERS),
+                ("b_sh", _vp * STAR_MAX_LAYERS)]
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -172,6 +185,11 @@ SIGNATURES = {
     "satrans_pnorm_workspace_floats": (C.c_int64, [C.POINTER(PNormDesc)]),
     "satrans_pnorm_fwd": (C.c_int, [C.POINTER(PNormDesc), _vp, _vp, _vp, _vp]),
     "satrans_pnorm_bwd": (C.c_int, [C.POINTER(PNormDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "satrans_star_saved_floats": (C.c_int64, [C.POINTER(StarDesc)]),
+    "satrans_star_workspace_floats": (C.c_int64, [C.POINTER(StarDesc)]),
+    "satrans_star_fwd": (C.c_int, [C.POINTER(StarDesc), _vp, _vp, _vp]),
+    "satrans_star_bwd": (C.c_int, [C.POINTER(StarDesc), _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
+                                   C.POINTER(_vp), _vp]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
