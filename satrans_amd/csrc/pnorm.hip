@@ -1,13 +1,10 @@
 // Partitioned normalisation: one batch-norm per scenario (the reference's MDR_BatchNorm, models/submodules.py:107-175, as
 // star.py:147-154 loops over it), every scenario of a batch in one pass.
 //
-// Layout.  x [B,C] stays in the caller's row order; `order` / `seg` (satrans_bucket_scenarios) give every scenario's run of rows.
-// A run is cut into chunks of kRowChunk rows; a workgroup owns (one chunk) x (one tile of kChanTile adjacent channels).  Its
-// 64 lanes run along the channels, so a wave reads 256 contiguous bytes of a row; its kWaves waves take the chunk's rows
-// round-robin (wave w: rows w, w + kWaves, ...), kRowsPerThread rows per lane, all loaded before the first use.
-// The number of chunks depends on seg, which lives on the device: the grid is sized for the most a batch can have,
-// ceil(B / kRowChunk) + S "slots", and a workgroup finds (scenario, chunk) of its slot by walking seg; a slot past the last
-// chunk ends at once.  Nothing is read back to the host.
+// Layout.  x [B,C] stays in the caller's row order; a scenario's run is cut into chunks of kRowChunk rows and the grid is sized
+// in slots, as seg_walk.h describes.  A workgroup owns (one chunk) x (one tile of kChanTile adjacent channels).  Its 64 lanes
+// run along the channels, so a wave reads 256 contiguous bytes of a row; its kWaves waves take the chunk's rows round-robin
+// (wave w: rows w, w + kWaves, ...), kRowsPerThread rows per lane, all loaded before the first use.
 //
 // Reduction order (fixed; no floating-point atomics, so equal inputs give equal bits):
 //   lane     its <= kRowsPerThread rows around a pivot (its first row): d = x - pivot is exact for values of one magnitude,
@@ -16,7 +13,7 @@
 //   finalise the chunks of a (scenario, channel): kGroups groups merge contiguous shares in chunk order, then the group
 //            results in group order.  The merges run in fp64 (a handful per channel); the stored partials are fp32.
 // The backward's two sums (dy, dy * xhat) go the same way with plain additions.
-#include "common.h"
+#include "seg_walk.h"
 
 namespace satrans {
 namespace {
@@ -31,53 +28,9 @@ static_assert(kChanTile == kWave, "lanes run along the channels of a tile");
 static_assert(kRowChunk % kWaves == 0 && kRowsPerThread <= 32, "row mask is 32 bits");
 static_assert(kGroups == kWaves, "the finalise kernels reuse the block shape");
 
-struct Slot {
-    int s, r0, r1, n;      // scenario, positions [r0, r1) of `order`, rows of the whole scenario;  s < 0: no such chunk
-};
-
-__device__ __forceinline__ int chunks_of(int n) { return n > 0 ? (n + kRowChunk - 1) / kRowChunk : 0; }
-
-// rows of scenario s, with seg clipped into [0, B] so that a damaged seg cannot send a read outside `order`
-__device__ __forceinline__ void seg_range(const int32_t* __restrict__ seg, int s, int B, int& a, int& b) {
-    a = min(max(seg[s], 0), B);
-    b = min(max(seg[s + 1], a), B);
-}
-
-__device__ __forceinline__ Slot find_slot(const int32_t* __restrict__ seg, int S, int B, int slot) {
-    int cum = 0;
-    for (int s = 0; s < S; ++s) {
-        int a, b;
-        seg_range(seg, s, B, a, b);
-        const int nch = chunks_of(b - a);
-        if (slot < cum + nch) {
-            const int r0 = a + (slot - cum) * kRowChunk;
-            return Slot{s, r0, min(r0 + kRowChunk, b), b - a};
-        }
-        cum += nch;
-    }
-    return Slot{-1, 0, 0, 0};
-}
-
-// first slot and number of chunks of scenario s
-__device__ __forceinline__ void scenario_slots(const int32_t* __restrict__ seg, int s, int B, int& k0, int& nch, int& n) {
-    k0 = 0;
-    for (int t = 0; t < s; ++t) {
-        int a, b;
-        seg_range(seg, t, B, a, b);
-        k0 += chunks_of(b - a);
-    }
-    int a, b;
-    seg_range(seg, s, B, a, b);
-    n = b - a;
-    nch = chunks_of(n);
-}
-
 // row j of wave w in the chunk, or -1
-__device__ __forceinline__ int chunk_row(const int32_t* __restrict__ order, const Slot& sl, int w, int j, int B) {
-    const int p = sl.r0 + w + j * kWaves;
-    if (p >= sl.r1) return -1;
-    const int row = order[p];
-    return (unsigned)row < (unsigned)B ? row : -1;
+__device__ __forceinline__ int chunk_row(const int32_t* __restrict__ order, const SegSlotN& sl, int w, int j, int B) {
+    return row_at(order, sl.r0 + w + j * kWaves, sl.r1, B);
 }
 
 struct Moments {
@@ -105,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void pnorm_stats_kernel(const float* __re
                                                                float* __restrict__ part) {
     __shared__ float sh[3][kWaves][kChanTile];
     const int slot = blockIdx.x / ctiles, ct = blockIdx.x % ctiles;
-    const Slot sl = find_slot(seg, S, B, slot);
+    const SegSlotN sl = find_slot<SegSlotN>(seg, S, B, slot, kRowChunk);
     if (sl.s < 0) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = ct * kChanTile + lane;
     float cnt = 0.f, mean = 0.f, m2 = 0.f;
@@ -163,8 +116,7 @@ __global__ __launch_bounds__(kThreads) void pnorm_finalize_kernel(const float* _
                                                                   float* __restrict__ running_var) {
     __shared__ double sh[3][kGroups][kChanTile];
     const int s = blockIdx.y, lane = threadIdx.x & 63, g = threadIdx.x >> 6, c = blockIdx.x * kChanTile + lane;
-    int k0, nch, n;
-    scenario_slots(seg, s, B, k0, nch, n);
+    const int k0 = first_slot(seg, s, B, kRowChunk), nch = scenario_units(seg, s, B, kRowChunk);
     const int per = (nch + kGroups - 1) / kGroups;
     Moments m{0.0, 0.0, 0.0};
     if (c < C) {
@@ -213,7 +165,7 @@ __global__ __launch_bounds__(kThreads) void pnorm_apply_kernel(const float* __re
                                                                const float* __restrict__ bias, const float* __restrict__ shared_w,
                                                                const float* __restrict__ shared_b, float* __restrict__ y) {
     const int slot = blockIdx.x / ctiles, ct = blockIdx.x % ctiles;
-    const Slot sl = find_slot(seg, S, B, slot);
+    const SegSlotN sl = find_slot<SegSlotN>(seg, S, B, slot, kRowChunk);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = ct * kChanTile + lane;
     if (sl.s < 0 || c >= C) return;
     const size_t at = (size_t)sl.s * C + c;
@@ -235,7 +187,7 @@ __global__ __launch_bounds__(kThreads) void pnorm_bwd_stats_kernel(const float* 
                                                                    float* __restrict__ part) {
     __shared__ float sh[2][kWaves][kChanTile];
     const int slot = blockIdx.x / ctiles, ct = blockIdx.x % ctiles;
-    const Slot sl = find_slot(seg, S, B, slot);
+    const SegSlotN sl = find_slot<SegSlotN>(seg, S, B, slot, kRowChunk);
     if (sl.s < 0) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = ct * kChanTile + lane;
     float s_dy = 0.f, s_dyx = 0.f;
@@ -282,9 +234,7 @@ __global__ __launch_bounds__(kThreads) void pnorm_bwd_finalize_kernel(const floa
     double gsw = 0.0, gsb = 0.0;
     int k0 = 0;
     for (int s = 0; s < S; ++s) {
-        int a, b;
-        seg_range(seg, s, B, a, b);
-        const int nch = chunks_of(b - a), per = (nch + kGroups - 1) / kGroups;
+        const int nch = scenario_units(seg, s, B, kRowChunk), per = (nch + kGroups - 1) / kGroups;
         double t_dy = 0.0, t_dyx = 0.0;
         if (c < C) {
             for (int k = k0 + g * per; k < min(k0 + nch, k0 + (g + 1) * per); ++k) {
@@ -327,7 +277,7 @@ __global__ __launch_bounds__(kThreads) void pnorm_bwd_apply_kernel(const float* 
                                                                    const float* __restrict__ sums, const float* __restrict__ weight,
                                                                    const float* __restrict__ shared_w, float* __restrict__ dx) {
     const int slot = blockIdx.x / ctiles, ct = blockIdx.x % ctiles;
-    const Slot sl = find_slot(seg, S, B, slot);
+    const SegSlotN sl = find_slot<SegSlotN>(seg, S, B, slot, kRowChunk);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = ct * kChanTile + lane;
     if (sl.s < 0 || c >= C) return;
     const size_t at = (size_t)sl.s * C + c, SC = (size_t)S * C;
@@ -355,22 +305,9 @@ struct PnLayout {
     int64_t slots, ctiles, blocks, part, sums, total;
 };
 
-int pnorm_validate(const satrans_pnorm_desc* d, const char* who) {
-    SATRANS_REQUIRE(d, SATRANS_E_BADARG, "%s: null descriptor", who);
-    SATRANS_REQUIRE(d->B > 0 && d->C > 0 && d->S > 0, SATRANS_E_BADARG, "%s: bad sizes B=%d C=%d S=%d", who, d->B, d->C, d->S);
-    SATRANS_REQUIRE(!(d->flags & ~SATRANS_TRAIN), SATRANS_E_BADARG, "%s: flags %d (SATRANS_TRAIN is the only one)", who, d->flags);
-    SATRANS_REQUIRE(d->eps >= 0.f && d->factor >= 0.f && d->factor <= 1.f, SATRANS_E_BADARG, "%s: eps %g, factor %g", who,
-                    (double)d->eps, (double)d->factor);
-    SATRANS_REQUIRE(d->S <= 65535, SATRANS_E_UNSUPPORTED, "%s: S=%d scenarios (65535 at most)", who, d->S);
-    const int64_t slots = ceil_div(d->B, kRowChunk) + d->S, ctiles = ceil_div(d->C, kChanTile);
-    SATRANS_REQUIRE(slots * ctiles <= 0x7fffffffLL, SATRANS_E_UNSUPPORTED, "%s: B=%d x C=%d needs more than 2^31 workgroups", who,
-                    d->B, d->C);
-    return SATRANS_OK;
-}
-
 PnLayout pnorm_layout(const satrans_pnorm_desc* d) {
     PnLayout L;
-    L.slots = ceil_div(d->B, kRowChunk) + d->S;
+    L.slots = seg_slots(d->B, d->S, kRowChunk);
     L.ctiles = ceil_div(d->C, kChanTile);
     L.blocks = L.slots * L.ctiles;
     L.part = 0;
@@ -379,31 +316,47 @@ PnLayout pnorm_layout(const satrans_pnorm_desc* d) {
     return L;
 }
 
+// checks the descriptor and hands out its layout
+int pnorm_validate(const satrans_pnorm_desc* d, const char* who, PnLayout& L) {
+    SATRANS_REQUIRE(d, SATRANS_E_BADARG, "%s: null descriptor", who);
+    SATRANS_REQUIRE(d->B > 0 && d->C > 0 && d->S > 0, SATRANS_E_BADARG, "%s: bad sizes B=%d C=%d S=%d", who, d->B, d->C, d->S);
+    SATRANS_REQUIRE(!(d->flags & ~SATRANS_TRAIN), SATRANS_E_BADARG, "%s: flags %d (SATRANS_TRAIN is the only one)", who, d->flags);
+    SATRANS_REQUIRE(d->eps >= 0.f && d->factor >= 0.f && d->factor <= 1.f, SATRANS_E_BADARG, "%s: eps %g, factor %g", who,
+                    (double)d->eps, (double)d->factor);
+    SATRANS_REQUIRE(d->S <= 65535, SATRANS_E_UNSUPPORTED, "%s: S=%d scenarios (65535 at most)", who, d->S);
+    L = pnorm_layout(d);
+    SATRANS_REQUIRE(L.blocks <= 0x7fffffffLL, SATRANS_E_UNSUPPORTED, "%s: B=%d x C=%d needs more than 2^31 workgroups", who, d->B,
+                    d->C);
+    return SATRANS_OK;
+}
+
 }  // namespace
 }  // namespace satrans
 
 using namespace satrans;
 
 extern "C" int64_t satrans_pnorm_saved_floats(const satrans_pnorm_desc* d) {
-    const int rc = pnorm_validate(d, "pnorm_saved_floats");
+    PnLayout L;
+    const int rc = pnorm_validate(d, "pnorm_saved_floats", L);
     return rc ? rc : 2 * (int64_t)d->S * d->C;
 }
 
 extern "C" int64_t satrans_pnorm_workspace_floats(const satrans_pnorm_desc* d) {
-    const int rc = pnorm_validate(d, "pnorm_workspace_floats");
-    return rc ? rc : pnorm_layout(d).total;
+    PnLayout L;
+    const int rc = pnorm_validate(d, "pnorm_workspace_floats", L);
+    return rc ? rc : L.total;
 }
 
 extern "C" int satrans_pnorm_fwd(const satrans_pnorm_desc* d, float* y, float* saved, float* workspace, void* stream_) {
     hipStream_t st = (hipStream_t)stream_;
-    int rc = pnorm_validate(d, "pnorm_fwd");
+    PnLayout L;
+    int rc = pnorm_validate(d, "pnorm_fwd", L);
     if (rc) return rc;
     const bool batch_stats = d->flags & SATRANS_TRAIN;
     SATRANS_REQUIRE(d->x && d->order && d->seg && d->weight && d->bias && d->shared_w && d->shared_b && y && saved && workspace,
                     SATRANS_E_BADARG, "pnorm_fwd: null pointer");
     SATRANS_REQUIRE(!d->running_mean == !d->running_var, SATRANS_E_BADARG, "pnorm_fwd: running_mean without running_var (or the reverse)");
     SATRANS_REQUIRE(batch_stats || d->running_mean, SATRANS_E_BADARG, "pnorm_fwd: without SATRANS_TRAIN the running statistics normalise");
-    const PnLayout L = pnorm_layout(d);
     const int B = d->B, C = d->C, S = d->S, ctiles = (int)L.ctiles;
     if (batch_stats) {
         pnorm_stats_kernel<<<(unsigned)L.blocks, kThreads, 0, st>>>(d->x, d->order, d->seg, B, C, S, ctiles, workspace + L.part);
@@ -426,12 +379,12 @@ extern "C" int satrans_pnorm_fwd(const satrans_pnorm_desc* d, float* y, float* s
 extern "C" int satrans_pnorm_bwd(const satrans_pnorm_desc* d, const float* dy, float* dx, const float* saved, float* workspace,
                                  float* g_weight, float* g_bias, float* g_shared_w, float* g_shared_b, void* stream_) {
     hipStream_t st = (hipStream_t)stream_;
-    int rc = pnorm_validate(d, "pnorm_bwd");
+    PnLayout L;
+    int rc = pnorm_validate(d, "pnorm_bwd", L);
     if (rc) return rc;
     SATRANS_REQUIRE(d->x && d->order && d->seg && d->weight && d->shared_w && dy && dx && saved && workspace && g_weight && g_bias &&
                         g_shared_w && g_shared_b,
                     SATRANS_E_BADARG, "pnorm_bwd: null pointer");
-    const PnLayout L = pnorm_layout(d);
     const int B = d->B, C = d->C, S = d->S, ctiles = (int)L.ctiles;
     pnorm_bwd_stats_kernel<<<(unsigned)L.blocks, kThreads, 0, st>>>(d->x, dy, d->order, d->seg, B, C, S, ctiles, saved,
                                                                     workspace + L.part);

@@ -1,11 +1,9 @@
 // STAR's star-topology towers (reference models/star.py:156-170) for a mixed batch: every scenario's FC tower in one set of
 // launches.  Layer l of scenario s multiplies by W_eff[s,l] = W_dom[s,l] * W_sh[l] (elementwise) and adds b_dom[s,l] + b_sh[l].
 //
-// Layout.  x [B,C], the hidden rows, the dz rows and dx all stay in the caller's row order; `order` / `seg`
-// (satrans_bucket_scenarios) give every scenario's run of rows.  A run is cut into row tiles of kTM rows that never straddle a
-// scenario; a workgroup owns (one row tile) x (one tile of kTN output columns) and streams the contraction in steps of kTK.
-// The grid is sized for the most tiles a batch can have, ceil(B / kTM) + S slots; a workgroup finds (scenario, tile) of its slot
-// by walking seg, a slot past the last tile ends at once.  Nothing is read back to the host.
+// Layout.  x [B,C], the hidden rows, the dz rows and dx all stay in the caller's row order; a scenario's run is cut into row
+// tiles of kTM rows (products) or chunks of kDwChunk rows (weight gradients) and the grids are sized in slots, as seg_walk.h
+// describes.  A workgroup owns (one row tile) x (one tile of kTN output columns) and streams the contraction in steps of kTK.
 //
 // Products.  Exact f32-input MFMA (v_mfma_f32_32x32x2_f32): a result element is a k-ordered fmaf chain, so it does not depend on
 // the tile a row falls into.  The four waves of a workgroup take the 2 x 2 quadrants of its 64 x 64 tile, one 32 x 32
@@ -24,7 +22,7 @@
 // No floating-point atomics anywhere: equal inputs give equal bits, and a scenario's rows give the same bits alone as in a mix.
 #include <algorithm>
 
-#include "common.h"
+#include "seg_walk.h"
 
 namespace satrans {
 namespace {
@@ -40,40 +38,6 @@ static_assert(kTM == 64 && kTN == 64, "four waves take the 2 x 2 quadrants of 32
 static_assert(kDwChunk % kTK == 0 && kPer == 8, "tile loaders");
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-struct Tile {
-    int s, r0, r1;      // scenario, positions [r0, r1) of `order`;  s < 0: no such tile
-};
-
-__device__ __forceinline__ int tiles_of(int n, int rows) { return n > 0 ? (n + rows - 1) / rows : 0; }
-
-// rows of scenario s, with seg clipped into [0, B] so that a damaged seg cannot send a read outside `order`
-__device__ __forceinline__ void seg_range(const int32_t* __restrict__ seg, int s, int B, int& a, int& b) {
-    a = min(max(seg[s], 0), B);
-    b = min(max(seg[s + 1], a), B);
-}
-
-__device__ __forceinline__ Tile find_tile(const int32_t* __restrict__ seg, int S, int B, int slot, int rows) {
-    int cum = 0;
-    for (int s = 0; s < S; ++s) {
-        int a, b;
-        seg_range(seg, s, B, a, b);
-        const int nt = tiles_of(b - a, rows);
-        if (slot < cum + nt) {
-            const int r0 = a + (slot - cum) * rows;
-            return Tile{s, r0, min(r0 + rows, b)};
-        }
-        cum += nt;
-    }
-    return Tile{-1, 0, 0};
-}
-
-// row at position p of `order`, or -1
-__device__ __forceinline__ int row_at(const int32_t* __restrict__ order, int p, int r1, int B) {
-    if (p >= r1) return -1;
-    const int row = order[p];
-    return (unsigned)row < (unsigned)B ? row : -1;
-}
 
 // one contraction step of the workgroup's 64 x 64 tile: wave quadrant (wm, wn), A[i][k] = As[i][k], B[k][j] = Bs[j][k]
 __device__ __forceinline__ void mma_step(const float (*As)[kLd], const float (*Bs)[kLd], int lane, int wm, int wn, f32x16& acc) {
@@ -103,7 +67,7 @@ __global__ __launch_bounds__(kThreads) void star_gemm_kernel(const float* __rest
     __shared__ float Bs[kTN][kLd];
     __shared__ int rows_sh[kTM];
     const int slot = blockIdx.x / ntiles, n0 = (blockIdx.x % ntiles) * kTN;
-    const Tile tl = find_tile(seg, S, B, slot, kTM);
+    const SegSlot tl = find_slot<SegSlot>(seg, S, B, slot, kTM);
     if (tl.s < 0) return;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w & 1, wn = w >> 1;
     if (t < kTM) rows_sh[t] = row_at(order, tl.r0 + t, tl.r1, B);
@@ -180,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void star_dw_kernel(const float* __restri
     const int per_slot = ntiles * ktiles;
     const int slot = blockIdx.x / per_slot, rem = blockIdx.x % per_slot;
     const int n0 = (rem / ktiles) * kTM, c0 = (rem % ktiles) * kTN;
-    const Tile tl = find_tile(seg, S, B, slot, kDwChunk);
+    const SegSlot tl = find_slot<SegSlot>(seg, S, B, slot, kDwChunk);
     if (tl.s < 0) return;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w & 1, wn = w >> 1;
     const int jf = t & 63, kf0 = t >> 6;
@@ -238,9 +202,7 @@ __global__ __launch_bounds__(kThreads) void star_reduce_kernel(const float* __re
     double total = 0.0;
     int k0 = 0;
     for (int s = 0; s < S; ++s) {
-        int a, b;
-        seg_range(seg, s, B, a, b);
-        const int nch = tiles_of(b - a, kDwChunk);
+        const int nch = scenario_units(seg, s, B, kDwChunk);
         double sum = 0.0;
         for (int k = k0; k < k0 + nch; ++k) sum += part[(size_t)k * width + at];
         k0 += nch;
@@ -260,33 +222,10 @@ struct StarLayout {
     int64_t slots, dw_slots, hidden, max_w, dz, part, total;
 };
 
-int star_validate(const satrans_star_desc* d, const char* who) {
-    SATRANS_REQUIRE(d, SATRANS_E_BADARG, "%s: null descriptor", who);
-    SATRANS_REQUIRE(d->B > 0 && d->C > 0 && d->S > 0, SATRANS_E_BADARG, "%s: bad sizes B=%d C=%d S=%d", who, d->B, d->C, d->S);
-    SATRANS_REQUIRE(d->L >= 2 && d->L <= SATRANS_STAR_MAX_LAYERS, SATRANS_E_BADARG,
-                    "%s: bad sizes L=%d (1 to %d hidden layers and the logit layer)", who, d->L, SATRANS_STAR_MAX_LAYERS - 1);
-    for (int l = 0; l < d->L; ++l)
-        SATRANS_REQUIRE(d->width[l] > 0, SATRANS_E_BADARG, "%s: bad sizes width[%d]=%d", who, l, d->width[l]);
-    SATRANS_REQUIRE(d->width[d->L - 1] == 1, SATRANS_E_BADARG, "%s: bad sizes: the last layer has width 1, got %d", who,
-                    d->width[d->L - 1]);
-    SATRANS_REQUIRE(d->S <= 65535, SATRANS_E_UNSUPPORTED, "%s: S=%d scenarios (65535 at most)", who, d->S);
-    const int64_t slots = ceil_div(d->B, kTM) + d->S, dw_slots = ceil_div(d->B, kDwChunk) + d->S;
-    int64_t prev = d->C;
-    for (int l = 0; l < d->L; ++l) {
-        const int64_t n = d->width[l];
-        SATRANS_REQUIRE(n * prev <= 0x7fffffffLL && slots * ceil_div(std::max(n, prev), kTN) <= 0x7fffffffLL &&
-                            dw_slots * ceil_div(n, kTM) * ceil_div(prev, kTN) <= 0x7fffffffLL,
-                        SATRANS_E_UNSUPPORTED, "%s: layer %d (%lld x %lld) at B=%d needs more than 2^31 workgroups", who, l,
-                        (long long)n, (long long)prev, d->B);
-        prev = n;
-    }
-    return SATRANS_OK;
-}
-
 StarLayout star_layout(const satrans_star_desc* d) {
     StarLayout L;
-    L.slots = ceil_div(d->B, kTM) + d->S;
-    L.dw_slots = ceil_div(d->B, kDwChunk) + d->S;
+    L.slots = seg_slots(d->B, d->S, kTM);
+    L.dw_slots = seg_slots(d->B, d->S, kDwChunk);
     L.hidden = 0;
     L.max_w = 0;
     int64_t prev = d->C, per_chunk = 0;
@@ -305,6 +244,30 @@ StarLayout star_layout(const satrans_star_desc* d) {
     return L;
 }
 
+// checks the descriptor and hands out its layout
+int star_validate(const satrans_star_desc* d, const char* who, StarLayout& L) {
+    SATRANS_REQUIRE(d, SATRANS_E_BADARG, "%s: null descriptor", who);
+    SATRANS_REQUIRE(d->B > 0 && d->C > 0 && d->S > 0, SATRANS_E_BADARG, "%s: bad sizes B=%d C=%d S=%d", who, d->B, d->C, d->S);
+    SATRANS_REQUIRE(d->L >= 2 && d->L <= SATRANS_STAR_MAX_LAYERS, SATRANS_E_BADARG,
+                    "%s: bad sizes L=%d (1 to %d hidden layers and the logit layer)", who, d->L, SATRANS_STAR_MAX_LAYERS - 1);
+    for (int l = 0; l < d->L; ++l)
+        SATRANS_REQUIRE(d->width[l] > 0, SATRANS_E_BADARG, "%s: bad sizes width[%d]=%d", who, l, d->width[l]);
+    SATRANS_REQUIRE(d->width[d->L - 1] == 1, SATRANS_E_BADARG, "%s: bad sizes: the last layer has width 1, got %d", who,
+                    d->width[d->L - 1]);
+    SATRANS_REQUIRE(d->S <= 65535, SATRANS_E_UNSUPPORTED, "%s: S=%d scenarios (65535 at most)", who, d->S);
+    L = star_layout(d);
+    int64_t prev = d->C;
+    for (int l = 0; l < d->L; ++l) {
+        const int64_t n = d->width[l];
+        SATRANS_REQUIRE(n * prev <= 0x7fffffffLL && L.slots * ceil_div(std::max(n, prev), kTN) <= 0x7fffffffLL &&
+                            L.dw_slots * ceil_div(n, kTM) * ceil_div(prev, kTN) <= 0x7fffffffLL,
+                        SATRANS_E_UNSUPPORTED, "%s: layer %d (%lld x %lld) at B=%d needs more than 2^31 workgroups", who, l,
+                        (long long)n, (long long)prev, d->B);
+        prev = n;
+    }
+    return SATRANS_OK;
+}
+
 bool star_has_operands(const satrans_star_desc* d) {
     if (!d->x || !d->order || !d->seg) return false;
     for (int l = 0; l < d->L; ++l)
@@ -318,21 +281,23 @@ bool star_has_operands(const satrans_star_desc* d) {
 using namespace satrans;
 
 extern "C" int64_t satrans_star_saved_floats(const satrans_star_desc* d) {
-    const int rc = star_validate(d, "star_saved_floats");
-    return rc ? rc : (int64_t)d->B * star_layout(d).hidden;
+    StarLayout L;
+    const int rc = star_validate(d, "star_saved_floats", L);
+    return rc ? rc : (int64_t)d->B * L.hidden;
 }
 
 extern "C" int64_t satrans_star_workspace_floats(const satrans_star_desc* d) {
-    const int rc = star_validate(d, "star_workspace_floats");
-    return rc ? rc : star_layout(d).total;
+    StarLayout L;
+    const int rc = star_validate(d, "star_workspace_floats", L);
+    return rc ? rc : L.total;
 }
 
 extern "C" int satrans_star_fwd(const satrans_star_desc* d, float* logit, float* saved, void* stream_) {
     hipStream_t st = (hipStream_t)stream_;
-    const int rc = star_validate(d, "star_fwd");
+    StarLayout L;
+    const int rc = star_validate(d, "star_fwd", L);
     if (rc) return rc;
     SATRANS_REQUIRE(star_has_operands(d) && logit && saved, SATRANS_E_BADARG, "star_fwd: null pointer");
-    const StarLayout L = star_layout(d);
     const int B = d->B, S = d->S;
     const float* in = d->x;
     float* h = saved;
@@ -356,13 +321,13 @@ extern "C" int satrans_star_bwd(const satrans_star_desc* d, const float* dlogit,
                                 float* const* g_w_dom, float* const* g_b_dom, float* const* g_w_sh, float* const* g_b_sh,
                                 void* stream_) {
     hipStream_t st = (hipStream_t)stream_;
-    const int rc = star_validate(d, "star_bwd");
+    StarLayout L;
+    const int rc = star_validate(d, "star_bwd", L);
     if (rc) return rc;
     SATRANS_REQUIRE(star_has_operands(d) && dlogit && dx && saved && workspace && g_w_dom && g_b_dom && g_w_sh && g_b_sh,
                     SATRANS_E_BADARG, "star_bwd: null pointer");
     for (int l = 0; l < d->L; ++l)
         SATRANS_REQUIRE(g_w_dom[l] && g_b_dom[l] && g_w_sh[l] && g_b_sh[l], SATRANS_E_BADARG, "star_bwd: null pointer (layer %d)", l);
-    const StarLayout L = star_layout(d);
     const int B = d->B, S = d->S;
     // h_{l-1} of layer l: x for l = 0, else the saved rows of layer l - 1
     const float* hin[SATRANS_STAR_MAX_LAYERS];

@@ -129,14 +129,8 @@ class _MetaNetFn(torch.autograd.Function):
         B, F, D = x.shape
         S = table.shape[0]
         dev = x.device
-        i32 = dict(dtype=torch.int32, device=dev)
-        sid_in = scenario_ids.to(torch.int32).contiguous()
-        sid, order, seg = torch.empty(B, **i32), torch.empty(B, **i32), torch.empty(S + 1, **i32)
-        status = torch.zeros(1, **i32)
-        bucket = torch.empty(int(lib.satrans_bucket_workspace_bytes(B, S)), dtype=torch.uint8, device=dev)
+        order, seg, status = _launch_bucket(scenario_ids.to(torch.int32).contiguous(), B, S, dev)
         st = N.stream_handle(dev)
-        N.check(lib.satrans_bucket_scenarios(sid_in.data_ptr(), N.ID_I32, 1, 0, B, S, sid.data_ptr(), order.data_ptr(), seg.data_ptr(),
-                                             status.data_ptr(), bucket.data_ptr(), bucket.numel(), st), "satrans_bucket_scenarios")
         d = N.MetaNetDesc()
         d.B, d.F, d.D, d.U, d.S = B, F, D, mod.units[1], S
         d.flags = (N.TRAIN if mod.training else 0) | (0 if mod.use_norm else NO_NORM)
@@ -214,8 +208,8 @@ class _PNormFn(torch.autograd.Function):
         x, weight, bias = x.contiguous(), weight.contiguous(), bias.contiguous()
         shared_w, shared_b = shared_w.contiguous(), shared_b.contiguous()
         d = _pnorm_desc(x, weight, bias, shared_w, shared_b, order, seg, running_mean, running_var, factor, eps, batch_stats)
-        saved = torch.empty(_pnorm_size(lib.satrans_pnorm_saved_floats, d), dtype=torch.float32, device=dev)
-        work = torch.empty(_pnorm_size(lib.satrans_pnorm_workspace_floats, d), dtype=torch.float32, device=dev)
+        saved = torch.empty(_native_size(lib.satrans_pnorm_saved_floats, d), dtype=torch.float32, device=dev)
+        work = torch.empty(_native_size(lib.satrans_pnorm_workspace_floats, d), dtype=torch.float32, device=dev)
         y = torch.empty_like(x)
         N.check(lib.satrans_pnorm_fwd(C.byref(d), y.data_ptr(), saved.data_ptr(), work.data_ptr(), N.stream_handle(dev)),
                 "satrans_pnorm_fwd")
@@ -229,7 +223,7 @@ class _PNormFn(torch.autograd.Function):
         lib = N.lib()
         x, weight, bias, shared_w, shared_b, order, seg, saved = ctx.saved_tensors
         d = _pnorm_desc(x, weight, bias, shared_w, shared_b, order, seg, None, None, *ctx.args)
-        work = torch.empty(_pnorm_size(lib.satrans_pnorm_workspace_floats, d), dtype=torch.float32, device=x.device)
+        work = torch.empty(_native_size(lib.satrans_pnorm_workspace_floats, d), dtype=torch.float32, device=x.device)
         dx, g_w, g_b = torch.empty_like(x), torch.empty_like(weight), torch.empty_like(bias)
         g_sw, g_sb = torch.empty_like(shared_w), torch.empty_like(shared_b)
         N.check(lib.satrans_pnorm_bwd(C.byref(d), dy.contiguous().data_ptr(), dx.data_ptr(), saved.data_ptr(), work.data_ptr(),
@@ -249,7 +243,7 @@ def _pnorm_desc(x, weight, bias, shared_w, shared_b, order, seg, running_mean, r
     return d
 
 
-def _pnorm_size(fn, d):
+def _native_size(fn, d):
     n = int(fn(C.byref(d)))
     if n < 0:
         N.check(n, fn.__name__)
@@ -302,22 +296,28 @@ def _pnorm_run(bns, x, order, seg, counts, shared_weight, shared_bias, training)
     return y, saved.view(2, len(bns), -1)
 
 
-def _bucket_rows(x, domain_ids, S, domain_id_offset, what):
-    """Bucket the rows of x by scenario id - offset (satrans_bucket_scenarios) -> order [B], seg [S+1] on the device and the
-    host-side row counts.  One device-to-host read (the S + 1 segment bounds and the status word); an id outside
-    [offset, offset + S) raises IndexError."""
+def _launch_bucket(sid_in, B, S, dev):
+    """satrans_bucket_scenarios on B int32 ids -> order [B], seg [S+1], status [1] (non-zero: an id outside [0, S)); no read-back."""
     lib = N.lib()
-    B, dev = x.shape[0], x.device
-    if B == 0 or domain_ids.numel() != B:
-        raise ValueError(f"{what}: {B} rows with {domain_ids.numel()} scenario ids")
     i32 = dict(dtype=torch.int32, device=dev)
-    sid_in = (domain_ids.reshape(-1).to(device=dev, dtype=torch.int64) - int(domain_id_offset)).to(torch.int32).contiguous()
     sid, order, seg = torch.empty(B, **i32), torch.empty(B, **i32), torch.empty(S + 1, **i32)
     status = torch.zeros(1, **i32)
     bucket = torch.empty(int(lib.satrans_bucket_workspace_bytes(B, S)), dtype=torch.uint8, device=dev)
     N.check(lib.satrans_bucket_scenarios(sid_in.data_ptr(), N.ID_I32, 1, 0, B, S, sid.data_ptr(), order.data_ptr(), seg.data_ptr(),
                                          status.data_ptr(), bucket.data_ptr(), bucket.numel(), N.stream_handle(dev)),
             "satrans_bucket_scenarios")
+    return order, seg, status
+
+
+def _bucket_rows(x, domain_ids, S, domain_id_offset, what):
+    """Bucket the rows of x by scenario id - offset (satrans_bucket_scenarios) -> order [B], seg [S+1] on the device and the
+    host-side row counts.  One device-to-host read (the S + 1 segment bounds and the status word); an id outside
+    [offset, offset + S) raises IndexError."""
+    B, dev = x.shape[0], x.device
+    if B == 0 or domain_ids.numel() != B:
+        raise ValueError(f"{what}: {B} rows with {domain_ids.numel()} scenario ids")
+    sid_in = (domain_ids.reshape(-1).to(device=dev, dtype=torch.int64) - int(domain_id_offset)).to(torch.int32).contiguous()
+    order, seg, status = _launch_bucket(sid_in, B, S, dev)
     host = torch.cat([seg, status]).tolist()
     if host[-1] != 0:
         raise IndexError(f"{what}: a scenario id lies outside [{domain_id_offset}, {domain_id_offset + S})")
@@ -398,7 +398,7 @@ class _StarFn(torch.autograd.Function):
         x = x.contiguous()
         tensors = tuple(t.contiguous() for t in tensors)
         d = _star_desc(x, order, seg, L, tensors)
-        saved = torch.empty(_pnorm_size(lib.satrans_star_saved_floats, d), dtype=torch.float32, device=dev)
+        saved = torch.empty(_native_size(lib.satrans_star_saved_floats, d), dtype=torch.float32, device=dev)
         logit = torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev)
         N.check(lib.satrans_star_fwd(C.byref(d), logit.data_ptr(), saved.data_ptr(), N.stream_handle(dev)), "satrans_star_fwd")
         ctx.L = L
@@ -412,7 +412,7 @@ class _StarFn(torch.autograd.Function):
         x, order, seg, saved, *tensors = ctx.saved_tensors
         L = ctx.L
         d = _star_desc(x, order, seg, L, tensors)
-        work = torch.empty(_pnorm_size(lib.satrans_star_workspace_floats, d), dtype=torch.float32, device=x.device)
+        work = torch.empty(_native_size(lib.satrans_star_workspace_floats, d), dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x)
         grads = [torch.empty_like(t) for t in tensors]
         groups = [(C.c_void_p * L)(*[g.data_ptr() for g in grads[k * L:(k + 1) * L]]) for k in range(4)]

@@ -111,3 +111,18 @@ def assert_grad_close_but_for_kinks(got, want, atol, err_msg, frac=0.02, outlier
                                    err_msg=err_msg)
     assert float(bad.mean()) <= frac, (err_msg, "fraction outside the bound", float(bad.mean()))
     assert float(err.max()) <= outlier * float(np.abs(want).max()) + atol, (err_msg, float(err.max()), float(np.abs(want).max()))
+
+
+WORST = {}      # largest err / bound-scale seen per (tag, quantity) in this process; printed as it grows
+
+
+def check_close(tag, got, want, rel, msg, what="y", floor=0.0):
+    """Element-wise: |got - want| <= rel * max|want| + floor; the largest ratio seen is printed under `tag`."""
+    want = want.double()
+    scale = float(want.abs().max())
+    err = float((got.double() - want).abs().max())
+    key, ratio = (tag, f"{what} err / max"), err / max(scale, 1e-30)
+    if ratio > WORST.get(key, -1.0):
+        WORST[key] = ratio
+        print(f"[{tag}] largest {key[1]} so far: {ratio:.3e} ({msg})")
+    assert err <= rel * scale + floor, (msg, what, err, scale)

@@ -4,6 +4,8 @@ MDR_BatchNorm by the recorded runs of tests/test_mdr_bn_cpu.py.
 
 Bounds (the sibling bounds), all element-wise: y within 2e-5 max|y|; gradients within 1e-4 max|g| + 5e-9; the
 saved statistics and the buffers get the y bound relative to their own largest magnitude."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -11,6 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from satrans_amd import native
+from tests import helpers
 from tests import mdr_bn_reference as R
 
 pytestmark = pytest.mark.gpu
@@ -19,21 +22,7 @@ DEV = "cuda:0"
 CHUNK = native.PNORM_ROW_CHUNK
 S5, OFFSET = 5, 2
 GRADS = ("x", "weight", "bias", "shared_weight", "shared_bias")
-WORST = {}
-
-
-def _note(what, value, msg):
-    if value > WORST.get(what, -1.0):
-        WORST[what] = value
-        print(f"[mdr-bn-parity] largest {what} so far: {value:.3e} ({msg})")
-
-
-def check_close(got, want, rel, msg, what="y", floor=0.0):
-    want = want.double()
-    scale = float(want.abs().max())
-    err = float((got.double() - want).abs().max())
-    _note(f"{what} err / max", err / max(scale, 1e-30), msg)
-    assert err <= rel * scale + floor, (msg, what, err, scale)
+check_close = functools.partial(helpers.check_close, "mdr-bn-parity")
 
 
 def check_grads(got, want, msg):
@@ -135,6 +124,34 @@ def test_shape_sweep_against_the_restatement(C):
         check_close(y, y_ref, 2e-5, f"C={C} momentum={momentum} eval")
         check_grads(g, g_ref, f"C={C} momentum={momentum} eval")
         assert buffers(mod)[2] == [3] * S5
+
+
+def test_walker_edges_empty_first_scenario_and_an_exact_chunk():
+    """The walker's edges that the sweep skips: S = 4 with row counts [0, CHUNK, 0, 2] (the first scenario empty, a run of
+    exactly one chunk - no short last chunk - and an empty scenario between two runs), interleaved, a non-zero id offset,
+    C = 65 (one channel past a tile), training mode.  An empty scenario's saved statistics are exactly zero, its running
+    buffers untouched, its parameter gradients exactly zero."""
+    C, S, counts = 65, 4, [0, CHUNK, 0, 2]
+    ids = torch.cat([torch.full((n,), s) for s, n in enumerate(counts)])
+    ids = ids[torch.randperm(ids.numel(), generator=torch.Generator().manual_seed(41))]
+    assert [int((ids == s).sum()) for s in range(S)] == counts
+    x, w, P = draw(ids.numel(), C, S, 42, batches=1)
+    mod, st = make_pn(C, S, P).train(), ref_state(P)
+    y, g = run_pn(mod, x[0], ids + OFFSET, P, w, OFFSET)
+    y_ref, cache, g_ref = run_ref(st, x[0], ids, P, w, 0.1, True)
+    check_close(y, y_ref, 2e-5, "walker edges")
+    check_grads(g, g_ref, "walker edges")
+    stats = mod.last_stats.cpu()
+    check_close(stats[0], cache.mean, 2e-5, "walker edges", "saved mean")
+    check_close(stats[1], cache.invstd, 2e-5, "walker edges", "saved invstd")
+    rm, rv, nbt = buffers(mod)
+    check_close(rm, st.running_mean, 2e-5, "walker edges", "running_mean")
+    check_close(rv, st.running_var, 2e-5, "walker edges", "running_var")
+    assert nbt == st.num_batches_tracked == [1] * S
+    for s in (0, 2):
+        assert float(stats[:, s].abs().max()) == 0.0, s
+        assert torch.equal(rm[s], torch.zeros(C)) and torch.equal(rv[s], torch.ones(C)), s
+        assert float(g["weight"][s].abs().max()) == 0.0 and float(g["bias"][s].abs().max()) == 0.0, s
 
 
 def run_one(bn, x, sw, sb, w):

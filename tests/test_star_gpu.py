@@ -5,12 +5,15 @@ recorded runs of tests/test_star_cpu.py.
 Bounds (the sibling bounds), all element-wise: logit and saved hidden rows within 2e-5 max|.|; gradients within
 1e-4 max|g| + 5e-9; buffers get the output bound relative to their own largest magnitude.
 tests/test_star_cpu.py::test_premise_of_the_gpu_bounds pins their margin."""
+import functools
+
 import pytest
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from satrans_amd import native
+from tests import helpers
 from tests import mdr_bn_reference as BN
 from tests import star_reference as R
 
@@ -19,21 +22,7 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 TILE, CHUNK = native.STAR_ROW_TILE, native.STAR_DW_ROW_CHUNK
 S5, OFFSET = 5, 2
-WORST = {}
-
-
-def _note(what, value, msg):
-    if value > WORST.get(what, -1.0):
-        WORST[what] = value
-        print(f"[star-parity] largest {what} so far: {value:.3e} ({msg})")
-
-
-def check_close(got, want, rel, msg, what="y", floor=0.0):
-    want = want.double()
-    scale = float(want.abs().max())
-    err = float((got.double() - want).abs().max())
-    _note(f"{what} err / max", err / max(scale, 1e-30), msg)
-    assert err <= rel * scale + floor, (msg, what, err, scale)
+check_close = functools.partial(helpers.check_close, "star-parity")
 
 
 def check_grads(got, want, msg):
@@ -109,6 +98,28 @@ def test_shape_sweep_against_the_restatement(C, hidden):
         for l, t in enumerate(g[k]):
             assert float(t[4].abs().max()) == 0.0, (k, l)
     assert float(g["b_dom"][-1][2].abs().max()) > 0.0      # the one-row scenario is not skipped
+
+
+def test_walker_edges_empty_first_scenario_and_an_exact_chunk():
+    """The walker's edges that the sweep skips: S = 4 with row counts [0, CHUNK, 0, TILE + 1] (the first scenario empty, a run
+    of exactly one weight-gradient chunk = whole row tiles with no short last one, an empty scenario between two runs),
+    interleaved, a non-zero id offset.  The empty scenarios' parameter gradients are exactly zero."""
+    C, hidden, S, counts = 33, (48, 32), 4, [0, CHUNK, 0, TILE + 1]
+    ids = torch.cat([torch.full((n,), s) for s, n in enumerate(counts)])
+    ids = ids[torch.randperm(ids.numel(), generator=torch.Generator().manual_seed(41))]
+    assert [int((ids == s).sum()) for s in range(S)] == counts
+    x, w, P = R.draw(ids.numel(), C, hidden, S, 42)
+    mod = make_towers(C, hidden, S, P)
+    y, g = run(mod, x, ids + OFFSET, w, OFFSET)
+    y_ref, cache, g_ref = run_ref(x, ids, P, w)
+    check_close(y, y_ref, 2e-5, "walker edges")
+    for l, h in enumerate(mod.last_hidden):
+        check_close(h.cpu(), cache.h[l + 1], 2e-5, f"walker edges hidden {l}", "hidden")
+    check_grads(g, g_ref, "walker edges")
+    for k in ("w_dom", "b_dom"):
+        for l, t in enumerate(g[k]):
+            assert float(t[0].abs().max()) == 0.0 and float(t[2].abs().max()) == 0.0, (k, l)
+            assert float(t[1].abs().max()) > 0.0 and float(t[3].abs().max()) > 0.0, (k, l)
 
 
 def test_batch_smaller_than_a_tile():
