@@ -37,7 +37,7 @@ extern "C" {
  *    changed - so a caller built against the earlier version-7 header runs unchanged; the binding checks the new symbols at load.
  *    Likewise the instance-level attention search (satrans_attn_rule, satrans_attn_match, satrans_attn_inst_*) and the
  *    partitioned normalisation (satrans_pnorm_desc, satrans_pnorm_*), and after it STAR's star-topology towers
- *    (satrans_star_desc, satrans_star_*). */
+ *    (satrans_star_desc, satrans_star_*), and the scenario-routed MMoE head (satrans_mmoe_desc, satrans_mmoe_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -417,6 +417,67 @@ int64_t satrans_star_workspace_floats(const satrans_star_desc* d);
 int satrans_star_fwd(const satrans_star_desc* d, float* logit, float* saved, void* stream);
 int satrans_star_bwd(const satrans_star_desc* d, const float* dlogit, float* dx, const float* saved, float* workspace,
                      float* const* g_w_dom, float* const* g_b_dom, float* const* g_w_sh, float* const* g_b_sh, void* stream);
+
+/* Scenario-routed MMoE head (models/mmoe.py:142-171 under the per-scenario loss of mtl_basemodel.py:268-269) for a mixed batch:
+ * the E experts run over all rows, and row i of scenario (= task) t goes through task t's gate, mixture, tower and logit only.
+ *     experts   h^e_l = relu(h^e_{l-1} expert_w[l][e]^T + expert_b[l][e]),  h^e_0 = x,  l = 1 .. n_expert;  expert_out[e] = h^e_{n_expert}
+ *     gate      the DNN gate_w[l][t] / gate_b[l][t] (relu) over x, then scores = h gate_final_w[t]^T  [E]   (n_gate = 0: over x)
+ *     mixture   g = softmax(scores),  m = sum_e g[e] expert_out[e]
+ *     tower     the DNN tower_w[l][t] / tower_b[l][t] (relu) over m, then logit = h tower_final_w[t]^T + out_bias[t]
+ * x [B,C], logit / dlogit [B] and dx [B,C] in the caller's row order; order / seg from satrans_bucket_scenarios with S = T.
+ * Stacked parameters: expert_w[l] [E, n_l, n_{l-1}], expert_b[l] [E, n_l]; gate_w[l] [T, n_l, n_{l-1}], gate_b[l] [T, n_l],
+ * gate_final_w [T, E, n]; tower_w[l], tower_b[l] likewise, tower_final_w [T, 1, n], out_bias [T].
+ * fp32 throughout, products on the exact f32-input MFMA.  2 <= E <= SATRANS_MMOE_MAX_EXPERTS; 1 to SATRANS_MMOE_MAX_HIDDEN
+ * expert layers, 0 to SATRANS_MMOE_MAX_HIDDEN gate and tower layers; C and the widths are any positive integers.
+ * saved, from its start: the gates g [B,E], the mixture m [B, n of the last expert layer], the scores [B,E], then every hidden
+ * row in the caller's row order (experts [B, E n_l] with expert e in columns [e n_l, (e+1) n_l), gate, tower); the backward
+ * reads them (nothing is recomputed).  The forward needs no workspace; the backward's holds two [B, widest row] dz buffers,
+ * dscores [B,E] and the per-chunk partials of the weight gradients of the layer in hand (a chunk =
+ * SATRANS_MMOE_DW_ROW_CHUNK rows: counted from the start of a task's run for gate and tower, in the caller's row order for
+ * the experts).  The backward WRITES (does not accumulate) dx and every gradient of satrans_mmoe_grads, each of the shape of
+ * its parameter.  No floating-point atomics: chunks merge in chunk order, dx = experts' dx + gate's dx in that order, so equal
+ * inputs give equal bits and a task's rows give the same bits alone as inside a mixed batch (logit, dx, that task's gate,
+ * tower and out_bias gradients).  A task without rows gets zeros in its gradients. */
+#define SATRANS_MMOE_ROW_TILE 64
+#define SATRANS_MMOE_DW_ROW_CHUNK 256
+#define SATRANS_MMOE_MAX_EXPERTS 8
+#define SATRANS_MMOE_MAX_HIDDEN 3
+typedef struct satrans_mmoe_desc {
+    int32_t B, C, T, E;
+    int32_t n_expert, n_gate, n_tower;      /* hidden layers of the three DNNs */
+    int32_t reserved;                       /* 0 */
+    int32_t expert_width[SATRANS_MMOE_MAX_HIDDEN];
+    int32_t gate_width[SATRANS_MMOE_MAX_HIDDEN];
+    int32_t tower_width[SATRANS_MMOE_MAX_HIDDEN];
+    int32_t reserved2;                      /* 0 */
+    const float* x;
+    const int32_t *order, *seg;
+    const float* expert_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* expert_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* gate_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* gate_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* gate_final_w;
+    const float* tower_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* tower_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* tower_final_w;
+    const float* out_bias;
+} satrans_mmoe_desc;
+typedef struct satrans_mmoe_grads {
+    float* expert_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* expert_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* gate_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* gate_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* gate_final_w;
+    float* tower_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* tower_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* tower_final_w;
+    float* out_bias;
+} satrans_mmoe_grads;
+int64_t satrans_mmoe_saved_floats(const satrans_mmoe_desc* d);
+int64_t satrans_mmoe_workspace_floats(const satrans_mmoe_desc* d);
+int satrans_mmoe_fwd(const satrans_mmoe_desc* d, float* logit, float* saved, void* stream);
+int satrans_mmoe_bwd(const satrans_mmoe_desc* d, const float* dlogit, float* dx, const float* saved, float* workspace,
+                     const satrans_mmoe_grads* g, void* stream);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

@@ -15,7 +15,12 @@
     scenario's rows) for a mixed batch (csrc/star.hip), and `StarHead`, the scenario-dependent half of `Star_Net.forward`
     (star.py:144-173): the partitioned normalisation, then the towers, on one bucketing of the batch.
 
-All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip) wrapped in a
+  * `MMoEHead` - the expert / gate / tower half of the reference's MMOE.forward (models/mmoe.py:142-171) for a mixed batch
+    under the one-task-per-scenario loss of mtl_basemodel.py:268-269: the experts over all rows, each row through its own
+    task's gate, mixture, tower and logit only (csrc/mmoe.hip).
+
+All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
+csrc/mmoe.hip) wrapped in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -546,3 +551,157 @@ class StarHead(StarTowers):
             h, self.last_stats = _pnorm_run(list(self.bns), h, order, seg, counts, self.shared_bn_weight, self.shared_bn_bias,
                                             self.training)
         return self._run_towers(h, order, seg)
+
+
+def _mmoe_fill(d, x, order, seg, cfg, tensors, out=None):
+    """Fill a satrans_mmoe_desc (out is None) or the satrans_mmoe_grads `out` from `tensors`, which hold, in this order:
+    expert weights, expert biases, gate weights, gate biases, the gate's final weight, tower weights, tower biases, the tower's
+    final weight, the out biases (stacked over experts or tasks)."""
+    nx, ng, nt = cfg
+    it = iter(tensors)
+    tgt = d if out is None else out
+    for name, n in (("expert_w", nx), ("expert_b", nx), ("gate_w", ng), ("gate_b", ng)):
+        for l in range(n):
+            getattr(tgt, name)[l] = next(it).data_ptr()
+    tgt.gate_final_w = next(it).data_ptr()
+    for name, n in (("tower_w", nt), ("tower_b", nt)):
+        for l in range(n):
+            getattr(tgt, name)[l] = next(it).data_ptr()
+    tgt.tower_final_w = next(it).data_ptr()
+    tgt.out_bias = next(it).data_ptr()
+    if out is None:
+        d.B, d.C, d.T, d.E = x.shape[0], x.shape[1], tensors[-1].shape[0], tensors[0].shape[0]
+        d.n_expert, d.n_gate, d.n_tower = nx, ng, nt
+        d.x, d.order, d.seg = x.data_ptr(), order.data_ptr(), seg.data_ptr()
+        for l in range(nx):
+            d.expert_width[l] = tensors[l].shape[1]
+        for l in range(ng):
+            d.gate_width[l] = tensors[2 * nx + l].shape[1]
+        for l in range(nt):
+            d.tower_width[l] = tensors[2 * nx + 2 * ng + 1 + l].shape[1]
+    return tgt
+
+
+class _MMoEFn(torch.autograd.Function):
+    """logit [B,1] of the scenario-routed MMoE head (csrc/mmoe.hip); `tensors` as _mmoe_fill lists them."""
+
+    @staticmethod
+    def forward(ctx, x, order, seg, cfg, *tensors):
+        lib = N.lib()
+        dev = x.device
+        x = x.contiguous()
+        tensors = tuple(t.contiguous() for t in tensors)
+        d = _mmoe_fill(N.MMoEDesc(), x, order, seg, cfg, tensors)
+        saved = torch.empty(_native_size(lib.satrans_mmoe_saved_floats, d), dtype=torch.float32, device=dev)
+        logit = torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev)
+        N.check(lib.satrans_mmoe_fwd(C.byref(d), logit.data_ptr(), saved.data_ptr(), N.stream_handle(dev)), "satrans_mmoe_fwd")
+        ctx.cfg = cfg
+        ctx.save_for_backward(x, order, seg, saved, *tensors)
+        ctx.mark_non_differentiable(saved)
+        return logit, saved
+
+    @staticmethod
+    def backward(ctx, dlogit, _dsaved):
+        lib = N.lib()
+        x, order, seg, saved, *tensors = ctx.saved_tensors
+        d = _mmoe_fill(N.MMoEDesc(), x, order, seg, ctx.cfg, tensors)
+        work = torch.empty(_native_size(lib.satrans_mmoe_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        grads = [torch.empty_like(t) for t in tensors]
+        g = _mmoe_fill(d, x, order, seg, ctx.cfg, grads, out=N.MMoEGrads())
+        N.check(lib.satrans_mmoe_bwd(C.byref(d), dlogit.contiguous().data_ptr(), dx.data_ptr(), saved.data_ptr(), work.data_ptr(),
+                                     C.byref(g), N.stream_handle(x.device)), "satrans_mmoe_bwd")
+        return (dx, None, None, None, *grads)
+
+
+class _OutBias(nn.Module):
+    """The parameter of deepctr's PredictionLayer (state_dict key `bias`, shape [1], zeros); MMoEHead adds it to the logit."""
+
+    def __init__(self):
+        super().__init__()
+        self.bias = nn.Parameter(torch.zeros((1,)))
+
+
+class MMoEHead(nn.Module):
+    """The expert / gate / tower half of the reference's MMOE.forward (models/mmoe.py:142-171) over a mixed batch, for the
+    reference's one-task-per-scenario use (T = tasks = scenarios): the loss of mtl_basemodel.py:268-269 and predict (:376-378)
+    read, of a row's T outputs, only the column of the row's own scenario.  So the E experts run over all rows, and a row
+    whose id is t + domain_id_offset goes through task t's gate DNN and gate_dnn_final_layer, the softmax mixture of the
+    experts' outputs, task t's tower DNN and tower_dnn_final_layer, and out[t].bias - nothing of the other tasks.
+
+    Parameter names, shapes, state_dict order and initialisation are the reference MMOE's (DNN weights N(0, init_std), their
+    biases and the bias-free final nn.Linears torch's default, out.{t}.bias zeros): expert_dnn.{e}.linears.{l}.*,
+    gate_dnn.{t}.linears.{l}.* (only with gate hidden units), gate_dnn_final_layer.{t}.weight, tower_dnn.{t}.linears.{l}.*
+    (only with tower hidden units), tower_dnn_final_layer.{t}.weight, out.{t}.bias - those entries of a reference checkpoint
+    load with load_state_dict.
+
+    forward(dnn_input [B, inputs_dim] fp32, domain_ids [B], domain_id_offset=0) -> logit [B,1]; the caller applies the
+    sigmoid.  Per call: the ids are bucketed once (one device-to-host read), the per-task and per-expert parameters stacked
+    (torch.stack; autograd splits the gradients back), and one autograd.Function runs satrans_mmoe_fwd / satrans_mmoe_bwd.
+    `last_gates` [B, E] and `last_mixture` [B, last expert width] are views of the last forward's saved buffer.
+
+    Differences from the reference.  (1) The module returns each row's OWN task logit, [B,1], not the [B,T] matrix of all
+    tasks: the other T - 1 columns are never computed.  (2) l2_reg_dnn is not applied (main.py leaves it 0).  (3) An id
+    outside [offset, offset + num_tasks) raises IndexError; the reference's loss silently leaves such rows out.
+    Not built - NotImplementedError at construction: an activation other than relu, dropout, batch-norm inside the DNNs,
+    more than 8 experts, more than 3 hidden layers in a DNN, no expert layer."""
+
+    def __init__(self, inputs_dim, num_tasks, num_experts=3, expert_dnn_hidden_units=(256, 128), gate_dnn_hidden_units=(64,),
+                 tower_dnn_hidden_units=(64,), init_std=0.0001, dnn_activation='relu', dnn_dropout=0, dnn_use_bn=False):
+        super().__init__()
+        if dnn_activation != 'relu':
+            raise NotImplementedError(f"MMoEHead: activation {dnn_activation!r} is not built (relu only)")
+        if dnn_dropout != 0:
+            raise NotImplementedError("MMoEHead: dropout inside the DNNs is not built (dnn_dropout must be 0)")
+        if dnn_use_bn:
+            raise NotImplementedError("MMoEHead: batch-norm inside the DNNs is not built (dnn_use_bn must be False)")
+        if num_tasks <= 1:
+            raise ValueError("num_tasks must be greater than 1")
+        if num_experts <= 1:
+            raise ValueError("num_experts must be greater than 1")
+        if num_experts > N.MMOE_MAX_EXPERTS:
+            raise NotImplementedError(f"MMoEHead: 2 to {N.MMOE_MAX_EXPERTS} experts, got {num_experts}")
+        ex, ga, to = ([int(u) for u in units] for units in (expert_dnn_hidden_units, gate_dnn_hidden_units, tower_dnn_hidden_units))
+        if not 1 <= len(ex) <= N.MMOE_MAX_HIDDEN:
+            raise NotImplementedError(f"MMoEHead: 1 to {N.MMOE_MAX_HIDDEN} expert hidden layers, got {len(ex)}")
+        if len(ga) > N.MMOE_MAX_HIDDEN or len(to) > N.MMOE_MAX_HIDDEN:
+            raise NotImplementedError(f"MMoEHead: 0 to {N.MMOE_MAX_HIDDEN} gate and tower hidden layers, got {len(ga)} and {len(to)}")
+        if inputs_dim < 1 or min(ex + ga + to) < 1:
+            raise ValueError("MMoEHead: inputs_dim and the hidden units must be positive")
+        self.inputs_dim, self.num_tasks, self.num_experts = int(inputs_dim), int(num_tasks), int(num_experts)
+        self.expert_dnn_hidden_units, self.gate_dnn_hidden_units, self.tower_dnn_hidden_units = tuple(ex), tuple(ga), tuple(to)
+        T, E = self.num_tasks, self.num_experts
+        # (first: in the reference's state_dict `out.*` precedes MMOE's own modules, because its BaseModel registers that name)
+        self.out = nn.ModuleList([_OutBias() for _ in range(T)])
+        self.expert_dnn = nn.ModuleList([_TowerDNN(inputs_dim, ex, init_std) for _ in range(E)])
+        if ga:
+            self.gate_dnn = nn.ModuleList([_TowerDNN(inputs_dim, ga, init_std) for _ in range(T)])
+        self.gate_dnn_final_layer = nn.ModuleList([nn.Linear(ga[-1] if ga else inputs_dim, E, bias=False) for _ in range(T)])
+        if to:
+            self.tower_dnn = nn.ModuleList([_TowerDNN(ex[-1], to, init_std) for _ in range(T)])
+        self.tower_dnn_final_layer = nn.ModuleList([nn.Linear(to[-1] if to else ex[-1], 1, bias=False) for _ in range(T)])
+        self.last_gates = self.last_mixture = None
+
+    def forward(self, dnn_input, domain_ids, domain_id_offset=0):
+        x = dnn_input
+        if x.dim() != 2 or x.shape[1] != self.inputs_dim:
+            raise ValueError(f"MMoEHead: expected input [B, {self.inputs_dim}], got {tuple(x.shape)}")
+        N.require_gpu(x, "MMoEHead")
+        if x.dtype != torch.float32 or self.out[0].bias.dtype != torch.float32:
+            raise TypeError("MMoEHead: rows, parameters and gradients are float32")
+        order, seg, _ = _bucket_rows(x, domain_ids, self.num_tasks, domain_id_offset, "MMoEHead")
+        nx, ng, nt = len(self.expert_dnn_hidden_units), len(self.gate_dnn_hidden_units), len(self.tower_dnn_hidden_units)
+
+        def stacked(dnns, n):
+            layers = [[m.linears[l] for m in dnns] for l in range(n)]
+            return ([torch.stack([m.weight for m in layer]) for layer in layers] +
+                    [torch.stack([m.bias for m in layer]) for layer in layers])
+
+        tensors = (stacked(self.expert_dnn, nx) + (stacked(self.gate_dnn, ng) if ng else []) +
+                   [torch.stack([m.weight for m in self.gate_dnn_final_layer])] + (stacked(self.tower_dnn, nt) if nt else []) +
+                   [torch.stack([m.weight for m in self.tower_dnn_final_layer]), torch.cat([m.bias for m in self.out])])
+        logit, saved = _MMoEFn.apply(x, order, seg, (nx, ng, nt), *tensors)
+        B, E, n = x.shape[0], self.num_experts, self.expert_dnn_hidden_units[-1]
+        self.last_gates = saved[:B * E].view(B, E)
+        self.last_mixture = saved[B * E:B * (E + n)].view(B, n)
+        return logit

@@ -99,6 +99,33 @@ class StarDesc(C.Structure):
                 ("b_sh", _vp * STAR_MAX_LAYERS)]
 
 
+MMOE_ROW_TILE = 64           # SATRANS_MMOE_ROW_TILE: rows under a workgroup of the MMoE head's products
+MMOE_DW_ROW_CHUNK = 256      # SATRANS_MMOE_DW_ROW_CHUNK: rows that one partial of its weight gradients sums
+MMOE_MAX_EXPERTS = 8         # SATRANS_MMOE_MAX_EXPERTS
+MMOE_MAX_HIDDEN = 3          # SATRANS_MMOE_MAX_HIDDEN: hidden layers of the expert, gate and tower DNNs, each
+
+
+class MMoEDesc(C.Structure):
+    """Mirror of `satrans_mmoe_desc`."""
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("T", C.c_int32), ("E", C.c_int32), ("n_expert", C.c_int32),
+                ("n_gate", C.c_int32), ("n_tower", C.c_int32), ("reserved", C.c_int32),
+                ("expert_width", C.c_int32 * MMOE_MAX_HIDDEN), ("gate_width", C.c_int32 * MMOE_MAX_HIDDEN),
+                ("tower_width", C.c_int32 * MMOE_MAX_HIDDEN), ("reserved2", C.c_int32),
+                ("x", _vp), ("order", _vp), ("seg", _vp),
+                ("expert_w", _vp * MMOE_MAX_HIDDEN), ("expert_b", _vp * MMOE_MAX_HIDDEN),
+                ("gate_w", _vp * MMOE_MAX_HIDDEN), ("gate_b", _vp * MMOE_MAX_HIDDEN), ("gate_final_w", _vp),
+                ("tower_w", _vp * MMOE_MAX_HIDDEN), ("tower_b", _vp * MMOE_MAX_HIDDEN), ("tower_final_w", _vp),
+                ("out_bias", _vp)]
+
+
+class MMoEGrads(C.Structure):
+    """Mirror of `satrans_mmoe_grads`."""
+    _fields_ = [("expert_w", _vp * MMOE_MAX_HIDDEN), ("expert_b", _vp * MMOE_MAX_HIDDEN),
+                ("gate_w", _vp * MMOE_MAX_HIDDEN), ("gate_b", _vp * MMOE_MAX_HIDDEN), ("gate_final_w", _vp),
+                ("tower_w", _vp * MMOE_MAX_HIDDEN), ("tower_b", _vp * MMOE_MAX_HIDDEN), ("tower_final_w", _vp),
+                ("out_bias", _vp)]
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -190,6 +217,10 @@ SIGNATURES = {
     "satrans_star_fwd": (C.c_int, [C.POINTER(StarDesc), _vp, _vp, _vp]),
     "satrans_star_bwd": (C.c_int, [C.POINTER(StarDesc), _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp),
                                    C.POINTER(_vp), _vp]),
+    "satrans_mmoe_saved_floats": (C.c_int64, [C.POINTER(MMoEDesc)]),
+    "satrans_mmoe_workspace_floats": (C.c_int64, [C.POINTER(MMoEDesc)]),
+    "satrans_mmoe_fwd": (C.c_int, [C.POINTER(MMoEDesc), _vp, _vp, _vp]),
+    "satrans_mmoe_bwd": (C.c_int, [C.POINTER(MMoEDesc), _vp, _vp, _vp, _vp, C.POINTER(MMoEGrads), _vp]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
