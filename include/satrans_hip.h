@@ -37,7 +37,8 @@ extern "C" {
  *    changed - so a caller built against the earlier version-7 header runs unchanged; the binding checks the new symbols at load.
  *    Likewise the instance-level attention search (satrans_attn_rule, satrans_attn_match, satrans_attn_inst_*) and the
  *    partitioned normalisation (satrans_pnorm_desc, satrans_pnorm_*), and after it STAR's star-topology towers
- *    (satrans_star_desc, satrans_star_*), and the scenario-routed MMoE head (satrans_mmoe_desc, satrans_mmoe_*). */
+ *    (satrans_star_desc, satrans_star_*), the scenario-routed MMoE head (satrans_mmoe_desc, satrans_mmoe_*) and the
+ *    scenario-routed PLE head (satrans_ple_desc, satrans_ple_grads, satrans_ple_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -478,6 +479,94 @@ int64_t satrans_mmoe_workspace_floats(const satrans_mmoe_desc* d);
 int satrans_mmoe_fwd(const satrans_mmoe_desc* d, float* logit, float* saved, void* stream);
 int satrans_mmoe_bwd(const satrans_mmoe_desc* d, const float* dlogit, float* dx, const float* saved, float* workspace,
                      const satrans_mmoe_grads* g, void* stream);
+
+/* Scenario-routed PLE head (models/ple.py:161-248 under the per-scenario loss of mtl_basemodel.py:268-269) for a mixed batch,
+ * one or two CGC levels.  T tasks, ns specific experts per task, nsh shared experts; every expert is the relu DNN of widths
+ * expert_width, every gate the relu DNN of widths gate_width and a bias-free final layer.  Row i of task t = task[i]:
+ *   level 0 of two (dense unless stated): all E0 = T ns + nsh experts over x (blocks: task 0's ns, task 1's, ..., the shared);
+ *     own gate g0 (ROUTED: task t's) -> softmax over t's ns experts then the nsh shared ones -> own mixture;
+ *     shared gate sg0 -> softmax over all E0 blocks ascending -> shared mixture.
+ *   last level: task t's ns specific experts over the own mixture (ROUTED; over x with one level), the nsh shared experts over
+ *     the shared mixture (dense; over x with one level), task t's gate over the own mixture -> softmax over [specific, shared]
+ *     -> mixture -> task t's tower, tower_final_w and out_bias -> logit.  The last level's shared gate takes no part.
+ * Stacked parameters: e0_w[l] [E0, n_l, n_{l-1}], e0_b[l] [E0, n_l]; g0_w[l] [T, n_l, n_{l-1}], g0_b[l] [T, n_l], g0_final_w
+ * [T, ns + nsh, n]; sg0_w[l] [n_l, n_{l-1}], sg0_b[l] [n_l], sg0_final_w [E0, n]; spec_w[l] [T, ns, n_l, n_{l-1}], spec_b[l]
+ * [T, ns, n_l]; shared_w[l] [nsh, n_l, n_{l-1}], shared_b[l] [nsh, n_l]; gate_*, tower_*, out_bias as in satrans_mmoe_desc with
+ * E = ns + nsh.  With levels == 1 the e0 / g0 / sg0 fields and `task` are not read.
+ * x [B,C], logit / dlogit [B], dx [B,C], task [B] (int32, the row's task) in the caller's row order; order / seg from
+ * satrans_bucket_scenarios with S = T.  fp32 throughout, the products of the MMoE head (one more form: routed AND grouped
+ * within the task).  Limits: levels 1 or 2; nsh >= 1, ns >= 1, ns + nsh <= SATRANS_PLE_MAX_OWN; T ns + nsh <=
+ * SATRANS_PLE_MAX_SHARED_SCORES; 1 to SATRANS_PLE_MAX_HIDDEN expert layers, 0 to SATRANS_PLE_MAX_HIDDEN gate and tower layers.
+ * saved, from its start: the last level's gates [B, ns + nsh], mixture [B, n], scores, its hidden rows ([B, (ns + nsh) n_l]:
+ * the task's specific experts, then the shared ones), gate and tower rows; then, with two levels, own gates [B, ns + nsh],
+ * shared gates [B, E0], own mixture, shared mixture, both scores, level 0's hidden rows [B, E0 n_l] and both gates' rows.
+ * Nothing is recomputed.  The backward WRITES dx and every gradient of satrans_ple_grads.  No floating-point atomics; fixed
+ * orders: dx = level-0 experts' dx, + own gate's, + shared gate's (one level: specific experts', + shared experts', + gate's);
+ * d own mixture = specific experts' dx, + last-level gate's dx.  Equal inputs give equal bits; a task's rows give the same bits
+ * alone as inside a mix (logit, dx rows, the task's gates, last-level experts, tower, out_bias); the dense gradients sum
+ * over all rows in the caller's order (chunks of SATRANS_PLE_DW_ROW_CHUNK rows).  A task without rows gets zeros in its routed
+ * gradients. */
+#define SATRANS_PLE_ROW_TILE 64
+#define SATRANS_PLE_DW_ROW_CHUNK 256
+#define SATRANS_PLE_MAX_OWN 8
+#define SATRANS_PLE_MAX_SHARED_SCORES 64
+#define SATRANS_PLE_MAX_HIDDEN 3
+typedef struct satrans_ple_desc {
+    int32_t B, C, T, ns, nsh, levels;
+    int32_t n_expert, n_gate, n_tower;      /* hidden layers of the three kinds of DNN */
+    int32_t reserved;                       /* 0 */
+    int32_t expert_width[SATRANS_PLE_MAX_HIDDEN];
+    int32_t gate_width[SATRANS_PLE_MAX_HIDDEN];
+    int32_t tower_width[SATRANS_PLE_MAX_HIDDEN];
+    int32_t reserved2;                      /* 0 */
+    const float* x;
+    const int32_t *order, *seg, *task;
+    const float* e0_w[SATRANS_PLE_MAX_HIDDEN];
+    const float* e0_b[SATRANS_PLE_MAX_HIDDEN];
+    const float* g0_w[SATRANS_PLE_MAX_HIDDEN];
+    const float* g0_b[SATRANS_PLE_MAX_HIDDEN];
+    const float* g0_final_w;
+    const float* sg0_w[SATRANS_PLE_MAX_HIDDEN];
+    const float* sg0_b[SATRANS_PLE_MAX_HIDDEN];
+    const float* sg0_final_w;
+    const float* spec_w[SATRANS_PLE_MAX_HIDDEN];
+    const float* spec_b[SATRANS_PLE_MAX_HIDDEN];
+    const float* shared_w[SATRANS_PLE_MAX_HIDDEN];
+    const float* shared_b[SATRANS_PLE_MAX_HIDDEN];
+    const float* gate_w[SATRANS_PLE_MAX_HIDDEN];
+    const float* gate_b[SATRANS_PLE_MAX_HIDDEN];
+    const float* gate_final_w;
+    const float* tower_w[SATRANS_PLE_MAX_HIDDEN];
+    const float* tower_b[SATRANS_PLE_MAX_HIDDEN];
+    const float* tower_final_w;
+    const float* out_bias;
+} satrans_ple_desc;
+typedef struct satrans_ple_grads {
+    float* e0_w[SATRANS_PLE_MAX_HIDDEN];
+    float* e0_b[SATRANS_PLE_MAX_HIDDEN];
+    float* g0_w[SATRANS_PLE_MAX_HIDDEN];
+    float* g0_b[SATRANS_PLE_MAX_HIDDEN];
+    float* g0_final_w;
+    float* sg0_w[SATRANS_PLE_MAX_HIDDEN];
+    float* sg0_b[SATRANS_PLE_MAX_HIDDEN];
+    float* sg0_final_w;
+    float* spec_w[SATRANS_PLE_MAX_HIDDEN];
+    float* spec_b[SATRANS_PLE_MAX_HIDDEN];
+    float* shared_w[SATRANS_PLE_MAX_HIDDEN];
+    float* shared_b[SATRANS_PLE_MAX_HIDDEN];
+    float* gate_w[SATRANS_PLE_MAX_HIDDEN];
+    float* gate_b[SATRANS_PLE_MAX_HIDDEN];
+    float* gate_final_w;
+    float* tower_w[SATRANS_PLE_MAX_HIDDEN];
+    float* tower_b[SATRANS_PLE_MAX_HIDDEN];
+    float* tower_final_w;
+    float* out_bias;
+} satrans_ple_grads;
+int64_t satrans_ple_saved_floats(const satrans_ple_desc* d);
+int64_t satrans_ple_workspace_floats(const satrans_ple_desc* d);
+int satrans_ple_fwd(const satrans_ple_desc* d, float* logit, float* saved, void* stream);
+int satrans_ple_bwd(const satrans_ple_desc* d, const float* dlogit, float* dx, const float* saved, float* workspace,
+                    const satrans_ple_grads* g, void* stream);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

@@ -19,8 +19,12 @@
     under the one-task-per-scenario loss of mtl_basemodel.py:268-269: the experts over all rows, each row through its own
     task's gate, mixture, tower and logit only (csrc/mmoe.hip).
 
+  * `PLEHead` - the expert / gate / tower half of the reference's PLE.forward (models/ple.py:161-248), one or two CGC levels,
+    for a mixed batch under the same loss: what a row's own task needs is routed, what the shared mixture needs stays dense
+    (csrc/ple.hip).
+
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
-csrc/mmoe.hip) wrapped in a
+csrc/mmoe.hip, csrc/ple.hip) wrapped in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -702,6 +706,211 @@ class MMoEHead(nn.Module):
                    [torch.stack([m.weight for m in self.tower_dnn_final_layer]), torch.cat([m.bias for m in self.out])])
         logit, saved = _MMoEFn.apply(x, order, seg, (nx, ng, nt), *tensors)
         B, E, n = x.shape[0], self.num_experts, self.expert_dnn_hidden_units[-1]
+        self.last_gates = saved[:B * E].view(B, E)
+        self.last_mixture = saved[B * E:B * (E + n)].view(B, n)
+        return logit
+
+
+def _ple_counts(cfg):
+    """How many tensors each pointer of N.PLE_POINTERS takes from the list (0: not passed), for cfg = (levels, ns, nsh, nx, ng, nt)."""
+    levels, _, _, nx, ng, nt = cfg
+    per = {"e0": nx, "g0": ng, "sg0": ng, "spec": nx, "shared": nx, "gate": ng, "tower": nt}
+    out = []
+    for name, per_layer in N.PLE_POINTERS:
+        lower = name.split("_")[0] in ("e0", "g0", "sg0")
+        out.append((name, per_layer, 0 if lower and levels == 1 else (per[name.split("_")[0]] if per_layer else 1)))
+    return out
+
+
+def _ple_fill(tgt, cfg, tensors):
+    """Set the parameter pointers of a satrans_ple_desc or satrans_ple_grads from `tensors`, which follow N.PLE_POINTERS (a
+    per-layer pointer takes one tensor per hidden layer; the level-0 pointers take none with one level)."""
+    it = iter(tensors)
+    for name, per_layer, n in _ple_counts(cfg):
+        for l in range(n):
+            if per_layer:
+                getattr(tgt, name)[l] = next(it).data_ptr()
+            else:
+                setattr(tgt, name, next(it).data_ptr())
+    return tgt
+
+
+def _ple_desc(x, order, seg, task, cfg, widths, T, tensors):
+    d = _ple_fill(N.PLEDesc(), cfg, tensors)
+    d.B, d.C, d.T = x.shape[0], x.shape[1], T
+    d.levels, d.ns, d.nsh, d.n_expert, d.n_gate, d.n_tower = cfg
+    for arr, units in zip((d.expert_width, d.gate_width, d.tower_width), widths):
+        for l, n in enumerate(units):
+            arr[l] = n
+    d.x, d.order, d.seg, d.task = x.data_ptr(), order.data_ptr(), seg.data_ptr(), task.data_ptr()
+    return d
+
+
+class _PLEFn(torch.autograd.Function):
+    """logit [B,1] of the scenario-routed PLE head (csrc/ple.hip); `tensors` as _ple_fill lists them."""
+
+    @staticmethod
+    def forward(ctx, x, order, seg, task, cfg, widths, T, *tensors):
+        lib = N.lib()
+        dev = x.device
+        x = x.contiguous()
+        tensors = tuple(t.contiguous() for t in tensors)
+        d = _ple_desc(x, order, seg, task, cfg, widths, T, tensors)
+        saved = torch.empty(_native_size(lib.satrans_ple_saved_floats, d), dtype=torch.float32, device=dev)
+        logit = torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev)
+        N.check(lib.satrans_ple_fwd(C.byref(d), logit.data_ptr(), saved.data_ptr(), N.stream_handle(dev)), "satrans_ple_fwd")
+        ctx.cfg = (cfg, widths, T)
+        ctx.save_for_backward(x, order, seg, task, saved, *tensors)
+        ctx.mark_non_differentiable(saved)
+        return logit, saved
+
+    @staticmethod
+    def backward(ctx, dlogit, _dsaved):
+        lib = N.lib()
+        x, order, seg, task, saved, *tensors = ctx.saved_tensors
+        cfg, widths, T = ctx.cfg
+        d = _ple_desc(x, order, seg, task, cfg, widths, T, tensors)
+        work = torch.empty(_native_size(lib.satrans_ple_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        grads = [torch.empty_like(t) for t in tensors]
+        g = _ple_fill(N.PLEGrads(), cfg, grads)
+        N.check(lib.satrans_ple_bwd(C.byref(d), dlogit.contiguous().data_ptr(), dx.data_ptr(), saved.data_ptr(), work.data_ptr(),
+                                    C.byref(g), N.stream_handle(x.device)), "satrans_ple_bwd")
+        return (dx, None, None, None, None, None, None, *grads)
+
+
+class PLEHead(nn.Module):
+    """The expert / gate / tower half of the reference's PLE.forward (models/ple.py:161-248) over a mixed batch, for the
+    reference's one-task-per-scenario use (T = tasks = scenarios): the loss of mtl_basemodel.py:268-269 and predict read, of a
+    row's T outputs, only the column of the row's own scenario.  With two CGC levels a row whose id is t + domain_id_offset
+    therefore goes through: every level-0 expert (all T * specific + shared of them: the shared mixture needs each) and the
+    level-0 shared gate, as every row does; task t's level-0 gate and mixture over its own and the shared experts; on the last
+    level task t's specific experts, gate and mixture, the shared experts over the shared mixture, task t's tower and
+    out[t].bias - and nothing of the other tasks.  With one level only the last-level part exists, over dnn_input.
+
+    Parameter names, shapes, state_dict order and initialisation are the reference PLE's (DNN weights N(0, init_std), their
+    biases and the bias-free final nn.Linears torch's default, out.{t}.bias zeros): out.{t}.bias,
+    specific_experts.{level}.{task}.{j}.linears.{l}.*, shared_experts.{level}.0.{k}.linears.{l}.*,
+    specific_gate_dnn.{level}.{task}.0.linears.{l}.* and shared_gate_dnn.{level}.linears.{l}.* (only with gate hidden units),
+    specific_gate_dnn_final_layer.{level}.{task}.weight, shared_gate_dnn_final_layer.{level}.weight, tower_dnn.{t}.linears.{l}.*
+    (only with tower hidden units), tower_dnn_final_layer.{t}.weight - those entries of a reference checkpoint load with
+    load_state_dict.  Two kinds of parameter exist only for that and are never handed to the kernels; their .grad stays None,
+    exactly as in the reference: the LAST level's shared gate (its mixture feeds nothing), and shared_experts.{level}.0.{k} for
+    k >= shared_expert_num (the reference builds specific_expert_num shared experts per level and uses shared_expert_num).
+
+    forward(dnn_input [B, inputs_dim] fp32, domain_ids [B], domain_id_offset=0) -> logit [B,1]; the caller applies the
+    sigmoid.  Per call: the ids are bucketed once (one device-to-host read), the row-to-task array is formed, the parameters
+    stacked (torch.stack; autograd splits the gradients back), and one autograd.Function runs satrans_ple_fwd /
+    satrans_ple_bwd.  `last_gates` [B, specific + shared] and `last_mixture` [B, last expert width] are views of the last
+    forward's saved buffer, taken from the LAST level.  A task without rows gets zeros in its routed gradients.
+
+    Differences from the reference.  (1) The module returns each row's OWN task logit, [B,1], not the [B,T] matrix of all
+    tasks: the other T - 1 columns are never computed.  (2) l2_reg_dnn is not applied (main.py leaves it 0).  (3) One or two
+    levels: with three or more, the gates of levels below the last but one receive gradient from every row through the shared
+    mixture of the level above, so nothing is left to route there - a different kernel plan, not built.  (4) An id outside
+    [offset, offset + num_tasks) raises IndexError; the reference's loss silently leaves such rows out.
+    (5) shared_expert_num > specific_expert_num raises ValueError at construction; the reference raises IndexError in its
+    forward.  Not built - NotImplementedError at construction: num_levels outside {1, 2}, more than 8 experts under a task's
+    gate (specific + shared), more than 64 under the level-0 shared gate (num_tasks * specific + shared), more than 3 hidden
+    layers in a DNN, no expert layer, an activation other than relu, dropout, batch-norm inside the DNNs."""
+
+    def __init__(self, inputs_dim, num_tasks, shared_expert_num=1, specific_expert_num=1, num_levels=2,
+                 expert_dnn_hidden_units=(256, 128), gate_dnn_hidden_units=(64,), tower_dnn_hidden_units=(64,), init_std=0.0001,
+                 dnn_activation='relu', dnn_dropout=0, dnn_use_bn=False):
+        super().__init__()
+        if dnn_activation != 'relu':
+            raise NotImplementedError(f"PLEHead: activation {dnn_activation!r} is not built (relu only)")
+        if dnn_dropout != 0:
+            raise NotImplementedError("PLEHead: dropout inside the DNNs is not built (dnn_dropout must be 0)")
+        if dnn_use_bn:
+            raise NotImplementedError("PLEHead: batch-norm inside the DNNs is not built (dnn_use_bn must be False)")
+        if num_tasks <= 1:
+            raise ValueError("num_tasks must be greater than 1")
+        T, ns, nsh, levels = int(num_tasks), int(specific_expert_num), int(shared_expert_num), int(num_levels)
+        if nsh < 1 or ns < 1:
+            raise ValueError(f"PLEHead: shared_expert_num and specific_expert_num must be at least 1, got {nsh} and {ns}")
+        if nsh > ns:
+            raise ValueError(f"PLEHead: shared_expert_num {nsh} > specific_expert_num {ns}: the reference builds specific_expert_num "
+                             "shared experts per level and raises IndexError in its forward")
+        if levels not in (1, 2):
+            raise NotImplementedError(f"PLEHead: num_levels 1 or 2, got {num_levels}")
+        if ns + nsh > N.PLE_MAX_OWN:
+            raise NotImplementedError(f"PLEHead: specific + shared experts at most {N.PLE_MAX_OWN}, got {ns + nsh}")
+        if levels == 2 and T * ns + nsh > N.PLE_MAX_SHARED_SCORES:
+            raise NotImplementedError(f"PLEHead: num_tasks * specific + shared experts at most {N.PLE_MAX_SHARED_SCORES} under the "
+                                      f"level-0 shared gate, got {T * ns + nsh}")
+        ex, ga, to = ([int(u) for u in units] for units in (expert_dnn_hidden_units, gate_dnn_hidden_units, tower_dnn_hidden_units))
+        if not 1 <= len(ex) <= N.PLE_MAX_HIDDEN:
+            raise NotImplementedError(f"PLEHead: 1 to {N.PLE_MAX_HIDDEN} expert hidden layers, got {len(ex)}")
+        if len(ga) > N.PLE_MAX_HIDDEN or len(to) > N.PLE_MAX_HIDDEN:
+            raise NotImplementedError(f"PLEHead: 0 to {N.PLE_MAX_HIDDEN} gate and tower hidden layers, got {len(ga)} and {len(to)}")
+        if inputs_dim < 1 or min(ex + ga + to) < 1:
+            raise ValueError("PLEHead: inputs_dim and the hidden units must be positive")
+        self.inputs_dim, self.num_tasks, self.num_levels = int(inputs_dim), T, levels
+        self.shared_expert_num, self.specific_expert_num = nsh, ns
+        self.expert_dnn_hidden_units, self.gate_dnn_hidden_units, self.tower_dnn_hidden_units = tuple(ex), tuple(ga), tuple(to)
+        dim = lambda level: self.inputs_dim if level == 0 else ex[-1]      # noqa: E731
+        gate_in = lambda level: ga[-1] if ga else dim(level)      # noqa: E731
+        many = lambda level, tasks, count, units: nn.ModuleList(      # noqa: E731
+            [nn.ModuleList([_TowerDNN(dim(level), units, init_std) for _ in range(count)]) for _ in range(tasks)])
+        # (first: in the reference's state_dict `out.*` precedes PLE's own modules, because its BaseModel registers that name)
+        self.out = nn.ModuleList([_OutBias() for _ in range(T)])
+        self.specific_experts = nn.ModuleList([many(level, T, ns, ex) for level in range(levels)])
+        self.shared_experts = nn.ModuleList([many(level, 1, ns, ex) for level in range(levels)])      # ns of them: the reference's
+        if ga:
+            self.specific_gate_dnn = nn.ModuleList([many(level, T, 1, ga) for level in range(levels)])
+        self.specific_gate_dnn_final_layer = nn.ModuleList(
+            [nn.ModuleList([nn.Linear(gate_in(level), ns + nsh, bias=False) for _ in range(T)]) for level in range(levels)])
+        if ga:
+            self.shared_gate_dnn = nn.ModuleList([_TowerDNN(dim(level), ga, init_std) for level in range(levels)])
+        self.shared_gate_dnn_final_layer = nn.ModuleList(
+            [nn.Linear(gate_in(level), T * ns + nsh, bias=False) for level in range(levels)])
+        if to:
+            self.tower_dnn = nn.ModuleList([_TowerDNN(ex[-1], to, init_std) for _ in range(T)])
+        self.tower_dnn_final_layer = nn.ModuleList([nn.Linear(to[-1] if to else ex[-1], 1, bias=False) for _ in range(T)])
+        self.last_gates = self.last_mixture = None
+
+    def forward(self, dnn_input, domain_ids, domain_id_offset=0):
+        x = dnn_input
+        if x.dim() != 2 or x.shape[1] != self.inputs_dim:
+            raise ValueError(f"PLEHead: expected input [B, {self.inputs_dim}], got {tuple(x.shape)}")
+        N.require_gpu(x, "PLEHead")
+        if x.dtype != torch.float32 or self.out[0].bias.dtype != torch.float32:
+            raise TypeError("PLEHead: rows, parameters and gradients are float32")
+        T, ns, nsh, levels = self.num_tasks, self.specific_expert_num, self.shared_expert_num, self.num_levels
+        order, seg, _ = _bucket_rows(x, domain_ids, T, domain_id_offset, "PLEHead")
+        task = (domain_ids.reshape(-1).to(device=x.device, dtype=torch.int64) - int(domain_id_offset)).to(torch.int32).contiguous()
+        nx, ng, nt = len(self.expert_dnn_hidden_units), len(self.gate_dnn_hidden_units), len(self.tower_dnn_hidden_units)
+
+        def stacked(dnns, n):
+            layers = [[m.linears[l] for m in dnns] for l in range(n)]
+            return ([torch.stack([m.weight for m in layer]) for layer in layers] +
+                    [torch.stack([m.bias for m in layer]) for layer in layers])
+
+        def specific(level):
+            return [m for per_task in self.specific_experts[level] for m in per_task]
+
+        def shared(level):
+            return list(self.shared_experts[level][0])[:nsh]
+
+        def own_gate(level):
+            gate = stacked([self.specific_gate_dnn[level][t][0] for t in range(T)], ng) if ng else []
+            return gate + [torch.stack([m.weight for m in self.specific_gate_dnn_final_layer[level]])]
+
+        tensors = []
+        if levels == 2:
+            tensors += stacked(specific(0) + shared(0), nx) + own_gate(0)
+            if ng:
+                lin = self.shared_gate_dnn[0].linears
+                tensors += [m.weight for m in lin] + [m.bias for m in lin]
+            tensors.append(self.shared_gate_dnn_final_layer[0].weight)
+        last = levels - 1
+        tensors += stacked(specific(last), nx) + stacked(shared(last), nx) + own_gate(last)
+        tensors += (stacked(self.tower_dnn, nt) if nt else []) + [torch.stack([m.weight for m in self.tower_dnn_final_layer]),
+                                                                  torch.cat([m.bias for m in self.out])]
+        widths = (self.expert_dnn_hidden_units, self.gate_dnn_hidden_units, self.tower_dnn_hidden_units)
+        logit, saved = _PLEFn.apply(x, order, seg, task, (levels, ns, nsh, nx, ng, nt), widths, T, *tensors)
+        B, E, n = x.shape[0], ns + nsh, self.expert_dnn_hidden_units[-1]
         self.last_gates = saved[:B * E].view(B, E)
         self.last_mixture = saved[B * E:B * (E + n)].view(B, n)
         return logit

@@ -126,6 +126,34 @@ class MMoEGrads(C.Structure):
                 ("out_bias", _vp)]
 
 
+PLE_ROW_TILE = 64              # SATRANS_PLE_ROW_TILE
+PLE_DW_ROW_CHUNK = 256         # SATRANS_PLE_DW_ROW_CHUNK
+PLE_MAX_OWN = 8                # SATRANS_PLE_MAX_OWN: specific + shared experts of one task's gate
+PLE_MAX_SHARED_SCORES = 64     # SATRANS_PLE_MAX_SHARED_SCORES: T * specific + shared experts under the level-0 shared gate
+PLE_MAX_HIDDEN = 3             # SATRANS_PLE_MAX_HIDDEN: hidden layers of the expert, gate and tower DNNs, each
+
+# the parameter pointers of satrans_ple_desc / satrans_ple_grads in the header's order: (name, per hidden layer)
+PLE_POINTERS = (("e0_w", True), ("e0_b", True), ("g0_w", True), ("g0_b", True), ("g0_final_w", False), ("sg0_w", True),
+                ("sg0_b", True), ("sg0_final_w", False), ("spec_w", True), ("spec_b", True), ("shared_w", True), ("shared_b", True),
+                ("gate_w", True), ("gate_b", True), ("gate_final_w", False), ("tower_w", True), ("tower_b", True),
+                ("tower_final_w", False), ("out_bias", False))
+_PLE_POINTER_FIELDS = [(name, _vp * PLE_MAX_HIDDEN if per_layer else _vp) for name, per_layer in PLE_POINTERS]
+
+
+class PLEDesc(C.Structure):
+    """Mirror of `satrans_ple_desc`."""
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("T", C.c_int32), ("ns", C.c_int32), ("nsh", C.c_int32), ("levels", C.c_int32),
+                ("n_expert", C.c_int32), ("n_gate", C.c_int32), ("n_tower", C.c_int32), ("reserved", C.c_int32),
+                ("expert_width", C.c_int32 * PLE_MAX_HIDDEN), ("gate_width", C.c_int32 * PLE_MAX_HIDDEN),
+                ("tower_width", C.c_int32 * PLE_MAX_HIDDEN), ("reserved2", C.c_int32),
+                ("x", _vp), ("order", _vp), ("seg", _vp), ("task", _vp)] + _PLE_POINTER_FIELDS
+
+
+class PLEGrads(C.Structure):
+    """Mirror of `satrans_ple_grads`."""
+    _fields_ = list(_PLE_POINTER_FIELDS)
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -221,6 +249,10 @@ SIGNATURES = {
     "satrans_mmoe_workspace_floats": (C.c_int64, [C.POINTER(MMoEDesc)]),
     "satrans_mmoe_fwd": (C.c_int, [C.POINTER(MMoEDesc), _vp, _vp, _vp]),
     "satrans_mmoe_bwd": (C.c_int, [C.POINTER(MMoEDesc), _vp, _vp, _vp, _vp, C.POINTER(MMoEGrads), _vp]),
+    "satrans_ple_saved_floats": (C.c_int64, [C.POINTER(PLEDesc)]),
+    "satrans_ple_workspace_floats": (C.c_int64, [C.POINTER(PLEDesc)]),
+    "satrans_ple_fwd": (C.c_int, [C.POINTER(PLEDesc), _vp, _vp, _vp]),
+    "satrans_ple_bwd": (C.c_int, [C.POINTER(PLEDesc), _vp, _vp, _vp, _vp, C.POINTER(PLEGrads), _vp]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
