@@ -115,6 +115,16 @@ int satrans_bucket_scenarios(const void* X, int id_dtype, int64_t x_stride, int 
 int satrans_gather_fwd(const float* arena, const int64_t* row_span, const int32_t* cols, const void* X,
                        int id_dtype, int64_t x_stride, int B, int F, int D, float* out,
                        int32_t* rows_out, int32_t* status, void* stream);
+/* The grid of that launch, for a test that has to prove which of its loop trips it reaches: workgroups of SATRANS_GATHER_BLOCK
+ * threads, D/4 lanes per row, SATRANS_GATHER_ROWS_PER_THREAD rows per thread and trip, enough workgroups for every row once
+ * and never more than SATRANS_GATHER_MAX_BLOCKS (grid-strided beyond).  The pooled gather below is launched the same way
+ * (SATRANS_POOL_ITEMS (sample, field) items per thread and trip; its backward takes one).  Not part of what a caller relies on. */
+#define SATRANS_GATHER_BLOCK 256
+#define SATRANS_GATHER_ROWS_PER_THREAD 4
+#define SATRANS_GATHER_MAX_BLOCKS 2048
+#define SATRANS_POOL_BLOCK 256
+#define SATRANS_POOL_ITEMS 4
+#define SATRANS_POOL_MAX_BLOCKS 2048
 
 /* ------------------------------------------------------------------------------------------------
  * Pooled gather for models with VarLenSparseFeat fields: deepctr-torch's varlen_embedding_lookup + SequencePoolingLayer

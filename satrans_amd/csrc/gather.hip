@@ -14,8 +14,10 @@
 
 namespace satrans {
 
-constexpr int kGatherBlock = 256;
-constexpr int kRowsPerThread = 4;
+constexpr int kGatherBlock = SATRANS_GATHER_BLOCK;
+constexpr int kRowsPerThread = SATRANS_GATHER_ROWS_PER_THREAD;
+constexpr int kGatherMaxBlocks = SATRANS_GATHER_MAX_BLOCKS;      // 8 blocks per CU (256 CUs)
+static_assert(kGatherBlock == 256 && kRowsPerThread == 4 && kGatherMaxBlocks == 256 * 8, "the launch shape the kernel was tuned at");
 
 template <int LPR>  // lanes per row = D/4
 __global__ __launch_bounds__(kGatherBlock) void gather_rows_kernel(
@@ -374,7 +376,7 @@ extern "C" int satrans_gather_fwd(const float* arena, const int64_t* row_span, c
     const int lpr = D / 4;
     // enough threads for every row once, capped at 8 blocks per CU (256 CUs) and grid-strided beyond that
     int64_t blocks = ceil_div(ceil_div(n_rows, kRowsPerThread) * lpr, kGatherBlock);
-    if (blocks > 256 * 8) blocks = 256 * 8;
+    if (blocks > kGatherMaxBlocks) blocks = kGatherMaxBlocks;
     if (blocks < 1) blocks = 1;
 #define LAUNCH(LPR)                                                                                            \
     gather_rows_kernel<LPR><<<(unsigned)blocks, kGatherBlock, 0, stream>>>(                                    \

@@ -17,9 +17,11 @@
 
 namespace satrans {
 
-constexpr int kPoolBlock = 256;
-constexpr int kPoolItems = 4;
+constexpr int kPoolBlock = SATRANS_POOL_BLOCK;
+constexpr int kPoolItems = SATRANS_POOL_ITEMS;
 constexpr int kPoolSlotStep = 2;
+constexpr int kPoolMaxBlocks = SATRANS_POOL_MAX_BLOCKS;      // 8 blocks per CU (256 CUs)
+static_assert(kPoolBlock == 256 && kPoolItems == 4 && kPoolMaxBlocks == 256 * 8, "the launch shape the kernels were tuned at");
 
 struct PoolFields {
     satrans_pool_field f[SATRANS_POOL_MAX_FIELDS];
@@ -234,7 +236,7 @@ static int check_fields(const satrans_pool_field* fields, int F, int R, int Fv, 
 
 static int64_t pool_blocks(int64_t n_items, int lpr, int per_thread) {
     int64_t blocks = ceil_div(ceil_div(n_items, per_thread) * lpr, kPoolBlock);
-    if (blocks > 256 * 8) blocks = 256 * 8;      // 8 blocks per CU, grid-strided beyond that
+    if (blocks > kPoolMaxBlocks) blocks = kPoolMaxBlocks;      // 8 blocks per CU, grid-strided beyond that
     return blocks < 1 ? 1 : blocks;
 }
 

@@ -163,6 +163,9 @@ class PoolField(C.Structure):
 POOL_COPY, POOL_SUM, POOL_MEAN, POOL_MAX = 0, 1, 2, 3      # satrans_pool_field.combiner (SATRANS_POOL_*)
 POOL_MAX_LEN = 32                                           # SATRANS_POOL_MAX_LEN
 POOL_MAX_FIELDS = 64                                        # SATRANS_POOL_MAX_FIELDS
+# the launch grids of satrans_gather_fwd and satrans_pool_gather_fwd / satrans_pool_bwd (for tests that compute their trip counts)
+GATHER_BLOCK, GATHER_ROWS_PER_THREAD, GATHER_MAX_BLOCKS = 256, 4, 2048      # SATRANS_GATHER_*
+POOL_BLOCK, POOL_ITEMS, POOL_MAX_BLOCKS = 256, 4, 2048                      # SATRANS_POOL_BLOCK / _ITEMS / _MAX_BLOCKS
 
 
 class AdamHParams(C.Structure):

@@ -70,6 +70,95 @@ def test_pack_and_columns_lay_out_2d_blocks():
     assert np.array_equal(np.concatenate(cols, axis=1), packed)
 
 
+def _pin_cases():
+    from tests import test_varlen_golden as G
+    return list(G.CASES) + ["maxlen4_length"]
+
+
+@pytest.mark.parametrize("name", _pin_cases())
+def test_table_driven_reference_equals_the_model_restatement(name):
+    """`pooled_reference` (what the direct kernel tests of tests/test_pool_kernels_gpu.py compare with) on a model's own field
+    table and arena: its layer input is `layer_input`'s bit for bit - from float ids, from integer ids and from float ids with a
+    fraction (`.long()` truncates) - its rows are lo + id, its mask words are `slot_mask`'s bits, and `slot_gradients` is the
+    per-field autograd of `pool_rows`."""
+    from tests import test_varlen_golden as G
+    if name == "maxlen4_length":
+        model = V.build("cpu", ("mean", "max", "sum"), maxlen=4, length=True)
+        X, _ = V.batch(model, 40, seed=9)
+    else:
+        z, meta = G.load(name)
+        model = G.build(meta, "cpu")
+        X = torch.from_numpy(z["X"])
+    spec, vs = V.spec_of(model)
+    fields = V.pool_specs_of(model)
+    arena = model.embedding_arena.detach().clone()
+    D = model.embedding_size
+    want = V.layer_input(V.params(model, torch.float32), X, spec, vs)
+    ids = torch.ones(X.shape[1], dtype=torch.bool)                # (dense columns keep their values: they hold no ids)
+    for lo, hi in spec.dense:
+        ids[lo:hi] = False
+    Xi = torch.where(ids, X.long().float(), X)
+    forms = [X, torch.where(ids & (Xi >= 0), Xi + 0.25, Xi)] + ([X.long()] if bool(ids.all()) else [])
+    for Xf in forms:
+        got, rows, words = V.pooled_reference(arena, Xf, fields, D)
+        assert got.dtype == torch.float32 and torch.equal(got, want)
+        assert rows.dtype == torch.int32 and rows.shape == (X.shape[0], sum(f.maxlen for f in fields))
+        for f in fields:
+            assert torch.equal(rows[:, f.slot:f.slot + f.maxlen].long(), f.lo + X[:, f.col:f.col + f.maxlen].long())
+        for f, v in zip([f for f in fields if f.varlen >= 0], vs):
+            assert (f.col, f.maxlen, f.combiner, f.len_col) == (v.col, v.maxlen, v.combiner, -1 if v.len_col is None else v.len_col)
+            bits = (words[:, f.varlen].unsqueeze(1) >> torch.arange(f.maxlen)) & 1
+            assert torch.equal(bits.bool(), V.slot_mask(X, v)) and int(words[:, f.varlen].max()) < 2 ** f.maxlen
+    dx = torch.randn(want.shape, generator=torch.Generator().manual_seed(2))
+    g = V.slot_gradients(arena, X, fields, D, dx)
+    n_sparse = len(spec.sparse)
+    assert torch.equal(g[:, :n_sparse], dx[:, :n_sparse])
+    for i, (f, v) in enumerate(zip([f for f in fields if f.varlen >= 0], vs)):
+        table = model.embedding_dict[v.name].weight.detach()
+        E = table[X[:, v.col:v.col + v.maxlen].long()].clone().requires_grad_(True)
+        V.pool_rows(E, V.slot_mask(X, v), v).backward(dx[:, n_sparse + i])
+        assert torch.equal(g[:, f.slot:f.slot + f.maxlen], E.grad)
+
+
+def test_reference_max_gives_the_gradient_to_the_first_maximal_slot_at_32_slots():
+    """torch.max over 32 slots (the widest list) still returns the FIRST maximal slot - what the kernel's strict `>` keeps and what
+    the tests at maxlen 31 / 32 rely on: ties between neighbours, across the whole list and with every slot padding."""
+    g = torch.Generator().manual_seed(4)
+    v = V.VarSpec("", 0, 32, "max")
+    E = torch.randn(50, 32, 32, generator=g)
+    E[:10, 2] = E[:10, 1]
+    E[10:20, 31] = E[10:20, 0]
+    E[20:30] = E[20:30, :1]                                      # every slot equal
+    valid = torch.rand(50, 32, generator=g) < 0.7
+    valid[30:35] = False
+    valid[35:40] = True
+    E.requires_grad_(True)
+    dy = torch.randn(50, 32, generator=g)
+    V.pool_rows(E, valid, v).backward(dy)
+    w = E.detach() - (1 - valid.float().unsqueeze(-1)) * 1e9
+    top = w == w.max(1, keepdim=True)[0]
+    first = top & (top.long().cumsum(1) == 1)
+    assert int((top.sum(1) > 1).sum()) >= 10 * 32               # ties are there: every element of samples 20..29 at the least
+    assert torch.equal(E.grad, torch.where(first, dy.unsqueeze(1), torch.zeros_like(w)))
+
+
+def test_grid_constants_mirror_the_header():
+    """native.GATHER_* / POOL_* are the header's SATRANS_GATHER_* / SATRANS_POOL_* (the kernels define their launch shape from those)."""
+    import os
+    import re
+    from satrans_amd import native as N
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    header = open(os.path.join(root, "include", "satrans_hip.h")).read()
+    defs = {k: int(v) for k, v in re.findall(r"#define SATRANS_((?:GATHER|POOL)_[A-Z_]+) (\d+)\b", header)}
+    for k in ("GATHER_BLOCK", "GATHER_ROWS_PER_THREAD", "GATHER_MAX_BLOCKS", "POOL_BLOCK", "POOL_ITEMS", "POOL_MAX_BLOCKS",
+              "POOL_MAX_LEN", "POOL_MAX_FIELDS"):
+        assert getattr(N, k) == defs[k], k
+    for src, names in (("pool.hip", ("SATRANS_POOL_BLOCK", "SATRANS_POOL_ITEMS", "SATRANS_POOL_MAX_BLOCKS")),
+                       ("gather.hip", ("SATRANS_GATHER_BLOCK", "SATRANS_GATHER_ROWS_PER_THREAD", "SATRANS_GATHER_MAX_BLOCKS"))):
+        text = open(os.path.join(root, "satrans_amd", "csrc", src)).read()
+        assert all(n in text for n in names), src
+
+
 @pytest.mark.parametrize("combiner", ["sum", "mean", "max"])
 @pytest.mark.parametrize("length", [False, True])
 def test_reference_pooling_gradients_follow_autograd(combiner, length):

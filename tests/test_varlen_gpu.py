@@ -30,18 +30,23 @@ def _tie(model):
                 w[2] = w[1]
 
 
+def layer_input_and_reference(model, X, ids):
+    """(engine, its layer input [B, F, D] after a forward of X as float or int64 ids, the fp32 restatement's, the VarSpecs)"""
+    spec, vs = V.spec_of(model)
+    want = V.layer_input(V.params(model, torch.float32), X, spec, vs)
+    Xd = X.to(DEV) if ids == "f32" else X.long().to(DEV)
+    model(Xd)
+    eng = model._engine
+    return eng, eng.layer_outputs(X.shape[0])[0].cpu(), want, vs
+
+
 @pytest.mark.parametrize("combiner,length", FORMS)
 @pytest.mark.parametrize("ids", ["f32", "i64"])
 def test_pooled_gather_is_bit_exact(combiner, length, ids):
     model = _model((combiner, combiner), length=length)
     _tie(model)
     X, _ = V.batch(model, 96, seed=1)
-    spec, vs = V.spec_of(model)
-    want = V.layer_input(V.params(model, torch.float32), X, spec, vs)
-    Xd = X.to(DEV) if ids == "f32" else X.long().to(DEV)
-    model(Xd)
-    eng = model._engine
-    got = eng.layer_outputs(96)[0].cpu()
+    eng, got, want, vs = layer_input_and_reference(model, X, ids)
     assert torch.equal(got, want)
     empty = V.slot_mask(X, vs[0]).sum(1) == 0
     assert bool(empty.any())
@@ -67,12 +72,10 @@ def test_out_of_range_id_raises(where):
     model(X.to(DEV))                                              # the status word was cleared
 
 
-@pytest.mark.parametrize("combiner,length", FORMS)
-def test_pool_backward_is_bit_exact_per_slot(combiner, length):
-    model = _model((combiner, combiner), length=length)
-    _tie(model)
-    B = 64
-    X, _ = V.batch(model, B, seed=4)
+def check_slot_gradients(model, X):
+    """The pooling backward of a random dx after a forward of X: every slot's row gradient equals torch autograd through
+    `pool_rows` on an fp32 leaf of the gathered rows, bit for bit (5 sparse slots first: V.build's columns)."""
+    B = X.shape[0]
     spec, vs = V.spec_of(model)
     model(X.to(DEV))
     eng = model._engine
@@ -88,6 +91,15 @@ def test_pool_backward_is_bit_exact_per_slot(combiner, length):
         V.pool_rows(E, V.slot_mask(X, v), v).backward(g[:, 5 + i])
         assert torch.equal(gemb[:, slot:slot + v.maxlen], E.grad), v.name
         slot += v.maxlen
+    assert slot == eng.R
+
+
+@pytest.mark.parametrize("combiner,length", FORMS)
+def test_pool_backward_is_bit_exact_per_slot(combiner, length):
+    model = _model((combiner, combiner), length=length)
+    _tie(model)
+    X, _ = V.batch(model, 64, seed=4)
+    check_slot_gradients(model, X)
 
 
 CASES = [("sum", False, False), ("mean", False, False), ("max", False, False), ("mean", True, False), ("max", False, True)]
