@@ -38,7 +38,8 @@ extern "C" {
  *    Likewise the instance-level attention search (satrans_attn_rule, satrans_attn_match, satrans_attn_inst_*) and the
  *    partitioned normalisation (satrans_pnorm_desc, satrans_pnorm_*), and after it STAR's star-topology towers
  *    (satrans_star_desc, satrans_star_*), the scenario-routed MMoE head (satrans_mmoe_desc, satrans_mmoe_*) and the
- *    scenario-routed PLE head (satrans_ple_desc, satrans_ple_grads, satrans_ple_*). */
+ *    scenario-routed PLE head (satrans_ple_desc, satrans_ple_grads, satrans_ple_*), and AdaSparse's scenario-pruned DNN
+ *    (satrans_adasparse_desc, satrans_adasparse_grads, satrans_adasparse_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -577,6 +578,60 @@ int64_t satrans_ple_workspace_floats(const satrans_ple_desc* d);
 int satrans_ple_fwd(const satrans_ple_desc* d, float* logit, float* saved, void* stream);
 int satrans_ple_bwd(const satrans_ple_desc* d, const float* dlogit, float* dx, const float* saved, float* workspace,
                     const satrans_ple_grads* g, void* stream);
+
+/* AdaSparse's scenario-pruned DNN (models/adasparse.py:88-106 with use_bn = False, relu, no dropout) and the bias-free logit
+ * layer behind it (adasparse.py:185-189).  Nothing is routed: every row uses the same weights, and the scenario enters through
+ * the row's scenario embedding emb [B,E] only.  Layer l = 1 .. n_layers, h_0 = x [B,C], K = n_{l-1}, N = n_l = width[l-1]:
+ *     fc  = h_{l-1} lin_w[l]^T + lin_b[l]                      lin_w[l] [N, K],     lin_b[l] [N]
+ *     z   = [h_{l-1} | emb] prn_w[l]^T + prn_b[l]              prn_w[l] [N, K + E], prn_b[l] [N]
+ *     pi  = beta * sigmoid(alpha * z),  pi = 0 where |pi| - epsilon <= 0
+ *     h_l = relu(fc * pi)
+ *     logit = h_L final_w^T + out_bias[0]                      final_w [1, n_L], out_bias [1]
+ * fp32 throughout, products on the exact f32-input MFMA; the concatenation [h | emb] is never materialised (the forward
+ * layer is ONE launch: both products over one staged row tile, then the epilogue).  1 to SATRANS_MMOE_MAX_HIDDEN layers; C,
+ * E and the widths are any positive integers; beta > 0, epsilon >= 0.
+ * saved, from its start, per layer l: pi [B, n_l] (the pruned factors), dzf = fc alpha pi (1 - pi / beta) [B, n_l] (the forward
+ * forms 1 - pi / beta = sigmoid(-alpha z) from z, where it keeps its digits), h_l [B, n_l]; the backward reads them.  The forward needs no workspace.  The backward's holds two [B, widest layer] buffers
+ * of masked output gradients, [dfc | dz] [B, 2 widest layer] and the per-chunk partials of the weight gradients of the layer
+ * in hand (a chunk = SATRANS_MMOE_DW_ROW_CHUNK rows in the caller's row order).  With g = dh_l (fc pi > 0):
+ *     dfc = g pi,   dz = g dzf (exactly 0 where pruned),
+ *     dh_{l-1} = dfc lin_w[l] + dz prn_w[l][:, :K],   demb += dz prn_w[l][:, K:]  (last layer first),
+ *     d lin_w[l] = dfc^T h_{l-1},  d prn_w[l] = dz^T [h_{l-1} | emb],  d lin_b[l], d prn_b[l] = the column sums.
+ * The backward WRITES (does not accumulate) dx [B,C], demb [B,E] and every gradient of satrans_adasparse_grads, each of the
+ * shape of its parameter.  No floating-point atomics: chunks merge in chunk order and demb sums the layers last to first, so
+ * equal inputs give equal bits, and a row gives the same logit, dx and demb bits alone as inside any batch.
+ * final_w and out_bias both NULL: the DNN alone - no logit is written (h_L is the last [B, n_L] block of saved), the backward's
+ * `dlogit` is then dh_L [B, n_L] (put under h_L's relu mask there) and the two gradients of satrans_adasparse_grads are not written.
+ * satrans_adasparse_set_forward(1) makes the forward run each layer as two launches of the plain tile product (the second over
+ * a concatenated copy of [h | emb], kept behind the saved rows) and a pointwise kernel - the form the fused launch was measured
+ * against (tools/adasparse_time.py); 0, the default, is the fused launch.  Process-wide; the same mode must hold for the
+ * saved_floats call and the forward it sizes.  Returns the previous mode, or SATRANS_E_BADARG. */
+typedef struct satrans_adasparse_desc {
+    int32_t B, C, E, n_layers;
+    int32_t width[SATRANS_MMOE_MAX_HIDDEN];
+    float alpha, beta, epsilon;
+    const float *x, *emb;
+    const float* lin_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* lin_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* prn_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* prn_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* final_w;
+    const float* out_bias;
+} satrans_adasparse_desc;
+typedef struct satrans_adasparse_grads {
+    float* lin_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* lin_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* prn_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* prn_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* final_w;
+    float* out_bias;
+} satrans_adasparse_grads;
+int64_t satrans_adasparse_saved_floats(const satrans_adasparse_desc* d);
+int64_t satrans_adasparse_workspace_floats(const satrans_adasparse_desc* d);
+int satrans_adasparse_fwd(const satrans_adasparse_desc* d, float* logit, float* saved, void* stream);
+int satrans_adasparse_bwd(const satrans_adasparse_desc* d, const float* dlogit, float* dx, float* demb, const float* saved,
+                          float* workspace, const satrans_adasparse_grads* g, void* stream);
+int satrans_adasparse_set_forward(int composed);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

@@ -4,9 +4,9 @@ from .inputs import DenseFeat, SparseFeat, VarLenSparseFeat, build_input_feature
 from .callbacks import History  # noqa: F401
 from .basemodel import BaseModel  # noqa: F401
 from .satrans import SATrans  # noqa: F401
-from .layers import (MDR_BatchNorm, MetaTransformation, MMoEHead, PartitionedNorm, PLEHead, SelfAttention_Layer,  # noqa: F401
-                     StarHead, StarTowers)
+from .layers import (AdaSparseHead, MDR_BatchNorm, MetaTransformation, MMoEHead, PartitionedNorm, PLEHead, PrunedDNN,  # noqa: F401
+                     SelfAttention_Layer, StarHead, StarTowers)
 
 __all__ = ["SATrans", "BaseModel", "SparseFeat", "DenseFeat", "VarLenSparseFeat", "get_feature_names",
            "build_input_features", "History", "SelfAttention_Layer", "MetaTransformation",
-           "MDR_BatchNorm", "PartitionedNorm", "StarTowers", "StarHead", "MMoEHead", "PLEHead"]
+           "MDR_BatchNorm", "PartitionedNorm", "StarTowers", "StarHead", "MMoEHead", "PLEHead", "PrunedDNN", "AdaSparseHead"]

@@ -23,8 +23,12 @@
     for a mixed batch under the same loss: what a row's own task needs is routed, what the shared mixture needs stays dense
     (csrc/ple.hip).
 
+  * `PrunedDNN` - the reference's DNN_w_Pruner (models/adasparse.py:28-106): every layer's output times a scenario-aware
+    pruning factor cut to exactly zero below a threshold, both products of a layer in one launch; and `AdaSparseHead`, the
+    part of AdaSparse.forward behind the embeddings (adasparse.py:185-189).  Nothing is routed here (csrc/adasparse.hip).
+
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
-csrc/mmoe.hip, csrc/ple.hip) wrapped in a
+csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip) wrapped in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -914,3 +918,169 @@ class PLEHead(nn.Module):
         self.last_gates = saved[:B * E].view(B, E)
         self.last_mixture = saved[B * E:B * (E + n)].view(B, n)
         return logit
+
+
+def _adasparse_fill(tgt, L, tensors):
+    """Set the parameter pointers of a satrans_adasparse_desc / satrans_adasparse_grads from `tensors`: L linears weights, L
+    linears biases, L pruners weights, L pruners biases and, for the head, dnn_linear.weight and out.bias."""
+    it = iter(tensors)
+    for name, per_layer in N.ADASPARSE_POINTERS:
+        if per_layer:
+            for l in range(L):
+                getattr(tgt, name)[l] = next(it).data_ptr()
+        elif len(tensors) > 4 * L:
+            setattr(tgt, name, next(it).data_ptr())
+    return tgt
+
+
+def _adasparse_desc(x, emb, consts, L, tensors):
+    d = _adasparse_fill(N.AdaSparseDesc(), L, tensors)
+    d.B, d.C, d.E, d.n_layers = x.shape[0], x.shape[1], emb.shape[1], L
+    for l in range(L):
+        d.width[l] = tensors[l].shape[0]
+    d.alpha, d.beta, d.epsilon = consts
+    d.x, d.emb = x.data_ptr(), emb.data_ptr()
+    return d
+
+
+class _AdaSparseFn(torch.autograd.Function):
+    """The pruned DNN (csrc/adasparse.hip) over x [B,C] and the rows' scenario embeddings emb [B,E]; `tensors` as
+    _adasparse_fill lists them.  With the two head tensors the first output is the logit [B,1], without them h_L [B, n_L]."""
+
+    @staticmethod
+    def forward(ctx, x, emb, consts, L, *tensors):
+        lib = N.lib()
+        dev = x.device
+        x, emb = x.contiguous(), emb.contiguous()
+        tensors = tuple(t.contiguous() for t in tensors)
+        d = _adasparse_desc(x, emb, consts, L, tensors)
+        saved = torch.empty(_native_size(lib.satrans_adasparse_saved_floats, d), dtype=torch.float32, device=dev)
+        head = len(tensors) > 4 * L
+        B, n_last = x.shape[0], tensors[L - 1].shape[0]
+        logit = torch.empty(B, 1, dtype=torch.float32, device=dev) if head else None
+        N.check(lib.satrans_adasparse_fwd(C.byref(d), logit.data_ptr() if head else None, saved.data_ptr(), N.stream_handle(dev)),
+                "satrans_adasparse_fwd")
+        ctx.consts, ctx.L = consts, L
+        ctx.save_for_backward(x, emb, saved, *tensors)
+        ctx.mark_non_differentiable(saved)
+        if head:
+            return logit, saved
+        at = sum(3 * B * t.shape[0] for t in tensors[:L]) - B * n_last      # h_L: the last block of the last layer
+        return saved[at:at + B * n_last].view(B, n_last).clone(), saved
+
+    @staticmethod
+    def backward(ctx, dout, _dsaved):
+        lib = N.lib()
+        x, emb, saved, *tensors = ctx.saved_tensors
+        d = _adasparse_desc(x, emb, ctx.consts, ctx.L, tensors)
+        work = torch.empty(_native_size(lib.satrans_adasparse_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx, demb = torch.empty_like(x), torch.empty_like(emb)
+        grads = [torch.empty_like(t) for t in tensors]
+        g = _adasparse_fill(N.AdaSparseGrads(), ctx.L, grads)
+        N.check(lib.satrans_adasparse_bwd(C.byref(d), dout.contiguous().data_ptr(), dx.data_ptr(), demb.data_ptr(), saved.data_ptr(),
+                                          work.data_ptr(), C.byref(g), N.stream_handle(x.device)), "satrans_adasparse_bwd")
+        return (dx, demb, None, None, *grads)
+
+
+class PrunedDNN(nn.Module):
+    """AdaSparse's DNN with a scenario-aware pruner beside every layer - a drop-in for the reference's DNN_w_Pruner
+    (models/adasparse.py:28-106) as main.py configures it (relu, no dropout, no batch-norm).  Layer l computes
+
+        fc = linears[l](h),   pi = beta * sigmoid(alpha * pruners[l](cat([h, domain_embs], 1))),   pi[|pi| - epsilon <= 0] = 0,
+        h  = relu(fc * pi)
+
+    as ONE launch (both products over one staged row tile; the concatenation is never built).  Nothing is routed: every row
+    uses the same weights, the scenario enters through `domain_embs` only.  Parameters `linears.{l}.*` then `pruners.{l}.*`
+    with the reference's shapes and initialisation (linears weights N(0, init_std), everything else torch's default);
+    `alpha`, `beta`, `epsilon` are plain attributes as in the reference (1, 2.0, 0.25) and are read at every call.
+
+    forward(inputs [B, inputs_dim] fp32, domain_embs [B, domain_emb_dim] fp32) -> [B, hidden_units[-1]]; gradients flow to
+    both inputs.  `last_pi` is a list of [B, n_l] views of the last forward's saved buffer: the pruned factors, exactly 0
+    where a unit was pruned.
+
+    Not built - NotImplementedError at construction: an activation other than relu, dropout, use_bn, more than 3 hidden
+    layers.  ValueError for empty or non-positive widths.  beta must be positive and epsilon non-negative (ValueError at call)."""
+
+    def __init__(self, inputs_dim, hidden_units, domain_emb_dim=32, init_std=0.0001, activation='relu', dropout_rate=0, use_bn=False):
+        super().__init__()
+        what = type(self).__name__
+        if activation != 'relu':
+            raise NotImplementedError(f"{what}: activation {activation!r} is not built (relu only)")
+        if dropout_rate != 0:
+            raise NotImplementedError(f"{what}: dropout inside the DNN is not built (dropout_rate must be 0)")
+        if use_bn:
+            raise NotImplementedError(f"{what}: batch-norm inside the DNN is not built (use_bn must be False)")
+        hidden_units = [int(u) for u in hidden_units]
+        if len(hidden_units) == 0:
+            raise ValueError("hidden_units is empty!!")
+        if len(hidden_units) > N.MMOE_MAX_HIDDEN:
+            raise NotImplementedError(f"{what}: 1 to {N.MMOE_MAX_HIDDEN} hidden layers, got {len(hidden_units)}")
+        if inputs_dim < 1 or domain_emb_dim < 1 or min(hidden_units) < 1:
+            raise ValueError(f"{what}: inputs_dim, domain_emb_dim and hidden_units must be positive")
+        self.inputs_dim, self.hidden_units, self.domain_emb_dim = int(inputs_dim), tuple(hidden_units), int(domain_emb_dim)
+        units = [self.inputs_dim] + hidden_units
+        self.linears = nn.ModuleList([nn.Linear(units[i], units[i + 1]) for i in range(len(units) - 1)])
+        self.pruners = nn.ModuleList([nn.Linear(units[i] + self.domain_emb_dim, units[i + 1]) for i in range(len(units) - 1)])
+        for lin in self.linears:
+            nn.init.normal_(lin.weight, mean=0, std=init_std)
+        self.beta, self.epsilon, self.alpha = 2.0, 0.25, 1
+        self.last_pi = None
+
+    def _check(self, x, emb, what):
+        if x.dim() != 2 or x.shape[1] != self.inputs_dim:
+            raise ValueError(f"{what}: expected input [B, {self.inputs_dim}], got {tuple(x.shape)}")
+        if emb.dim() != 2 or emb.shape[1] != self.domain_emb_dim or emb.shape[0] != x.shape[0]:
+            raise ValueError(f"{what}: expected domain embeddings [{x.shape[0]}, {self.domain_emb_dim}], got {tuple(emb.shape)}")
+        N.require_gpu(x, what)
+        N.require_gpu(emb, what)
+        if x.dtype != torch.float32 or emb.dtype != torch.float32 or self.linears[0].weight.dtype != torch.float32:
+            raise TypeError(f"{what}: rows, parameters and gradients are float32")
+        if not (self.beta > 0 and self.epsilon >= 0):
+            raise ValueError(f"{what}: beta must be positive and epsilon non-negative, got {self.beta} and {self.epsilon}")
+
+    def _run(self, x, emb, head=()):
+        L = len(self.hidden_units)
+        tensors = ([m.weight for m in self.linears] + [m.bias for m in self.linears] + [m.weight for m in self.pruners] +
+                   [m.bias for m in self.pruners] + list(head))
+        out, saved = _AdaSparseFn.apply(x, emb, (float(self.alpha), float(self.beta), float(self.epsilon)), L, *tensors)
+        B, at, self.last_pi = x.shape[0], 0, []
+        for n in self.hidden_units:      # saved, per layer: pi, dzf, h
+            self.last_pi.append(saved[at:at + B * n].view(B, n))
+            at += 3 * B * n
+        return out
+
+    def forward(self, inputs, domain_embs):
+        self._check(inputs, domain_embs, "PrunedDNN")
+        return self._run(inputs, domain_embs)
+
+
+class AdaSparseHead(nn.Module):
+    """The part of the reference's AdaSparse.forward after the embeddings (models/adasparse.py:185-189): the pruned DNN, the
+    bias-free dnn_linear and the bias of the prediction layer.  state_dict keys and order are the reference's - out.bias,
+    dnn.linears.{l}.*, dnn.pruners.{l}.*, dnn_linear.weight - so those entries of a reference checkpoint load with
+    load_state_dict.  `dnn` is a PrunedDNN; set alpha, beta, epsilon there; `last_pi` is its.
+
+    forward(dnn_input [B, inputs_dim] fp32, domain_emb [B, domain_emb_dim] fp32) -> logit [B,1]; the caller applies the
+    sigmoid.  One autograd.Function runs the whole stack (satrans_adasparse_fwd / satrans_adasparse_bwd); gradients flow to
+    both inputs, so a `domain_emb` gathered from the model's own embedding table gives the table both of its gradient paths.
+
+    Differences from the reference.  (1) domain_emb must be [B, E]: the reference's `.squeeze()` turns a batch of one row into
+    [E] and then fails in its torch.cat; that quirk is not reproduced.  (2) l2_reg_dnn is not applied (main.py leaves it 0).
+    Not built: what PrunedDNN refuses."""
+
+    def __init__(self, inputs_dim, dnn_hidden_units=(256, 128), domain_emb_dim=32, init_std=0.0001, dnn_activation='relu',
+                 dnn_dropout=0, dnn_use_bn=False):
+        super().__init__()
+        # (first: in the reference's state_dict `out.*` precedes AdaSparse's own modules, because its BaseModel registers that name)
+        self.out = _OutBias()
+        self.dnn = PrunedDNN(inputs_dim, dnn_hidden_units, domain_emb_dim=domain_emb_dim, init_std=init_std, activation=dnn_activation,
+                             dropout_rate=dnn_dropout, use_bn=dnn_use_bn)
+        self.dnn_linear = nn.Linear(self.dnn.hidden_units[-1], 1, bias=False)
+
+    @property
+    def last_pi(self):
+        return self.dnn.last_pi
+
+    def forward(self, dnn_input, domain_emb):
+        self.dnn._check(dnn_input, domain_emb, "AdaSparseHead")
+        return self.dnn._run(dnn_input, domain_emb, head=(self.dnn_linear.weight, self.out.bias))

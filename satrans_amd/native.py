@@ -154,6 +154,23 @@ class PLEGrads(C.Structure):
     _fields_ = list(_PLE_POINTER_FIELDS)
 
 
+# the parameter pointers of satrans_adasparse_desc / satrans_adasparse_grads in the header's order: (name, per layer)
+ADASPARSE_POINTERS = (("lin_w", True), ("lin_b", True), ("prn_w", True), ("prn_b", True), ("final_w", False), ("out_bias", False))
+_ADASPARSE_POINTER_FIELDS = [(name, _vp * MMOE_MAX_HIDDEN if per_layer else _vp) for name, per_layer in ADASPARSE_POINTERS]
+
+
+class AdaSparseDesc(C.Structure):
+    """Mirror of `satrans_adasparse_desc`."""
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("E", C.c_int32), ("n_layers", C.c_int32),
+                ("width", C.c_int32 * MMOE_MAX_HIDDEN), ("alpha", C.c_float), ("beta", C.c_float), ("epsilon", C.c_float),
+                ("x", _vp), ("emb", _vp)] + _ADASPARSE_POINTER_FIELDS
+
+
+class AdaSparseGrads(C.Structure):
+    """Mirror of `satrans_adasparse_grads`."""
+    _fields_ = list(_ADASPARSE_POINTER_FIELDS)
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -256,6 +273,11 @@ SIGNATURES = {
     "satrans_ple_workspace_floats": (C.c_int64, [C.POINTER(PLEDesc)]),
     "satrans_ple_fwd": (C.c_int, [C.POINTER(PLEDesc), _vp, _vp, _vp]),
     "satrans_ple_bwd": (C.c_int, [C.POINTER(PLEDesc), _vp, _vp, _vp, _vp, C.POINTER(PLEGrads), _vp]),
+    "satrans_adasparse_saved_floats": (C.c_int64, [C.POINTER(AdaSparseDesc)]),
+    "satrans_adasparse_workspace_floats": (C.c_int64, [C.POINTER(AdaSparseDesc)]),
+    "satrans_adasparse_fwd": (C.c_int, [C.POINTER(AdaSparseDesc), _vp, _vp, _vp]),
+    "satrans_adasparse_bwd": (C.c_int, [C.POINTER(AdaSparseDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(AdaSparseGrads), _vp]),
+    "satrans_adasparse_set_forward": (C.c_int, [C.c_int]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
