@@ -39,7 +39,8 @@ extern "C" {
  *    partitioned normalisation (satrans_pnorm_desc, satrans_pnorm_*), and after it STAR's star-topology towers
  *    (satrans_star_desc, satrans_star_*), the scenario-routed MMoE head (satrans_mmoe_desc, satrans_mmoe_*) and the
  *    scenario-routed PLE head (satrans_ple_desc, satrans_ple_grads, satrans_ple_*), and AdaSparse's scenario-pruned DNN
- *    (satrans_adasparse_desc, satrans_adasparse_grads, satrans_adasparse_*). */
+ *    (satrans_adasparse_desc, satrans_adasparse_grads, satrans_adasparse_*), and the scenario-routed SharedBottom head
+ *    (satrans_sharedbottom_desc, satrans_sharedbottom_grads, satrans_sharedbottom_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -632,6 +633,62 @@ int satrans_adasparse_fwd(const satrans_adasparse_desc* d, float* logit, float* 
 int satrans_adasparse_bwd(const satrans_adasparse_desc* d, const float* dlogit, float* dx, float* demb, const float* saved,
                           float* workspace, const satrans_adasparse_grads* g, void* stream);
 int satrans_adasparse_set_forward(int composed);
+
+/* Scenario-routed SharedBottom head (models/sharedbottom.py:120-133 under the per-scenario loss of mtl_basemodel.py:268-269)
+ * for a mixed batch: the bottom DNN runs over all rows, and row i of scenario (= task) t goes through task t's tower only.
+ *     bottom    h_l = relu(h_{l-1} bottom_w[l]^T + bottom_b[l]),  h_0 = x,  l = 1 .. n_bottom                      (all rows)
+ *     tower     the DNN tower_w[l][t] / tower_b[l][t] (relu) over the bottom's last rows, then
+ *               logit = h tower_final_w[t]^T + out_bias[t]                       (n_tower = 0: over the bottom's last rows)
+ * x [B,C], logit / dlogit [B] and dx [B,C] in the caller's row order; order / seg from satrans_bucket_scenarios with S = T.
+ * bottom_w[l] [n_l, n_{l-1}], bottom_b[l] [n_l]; tower_w[l] [T, n_l, n_{l-1}], tower_b[l] [T, n_l], tower_final_w [T, 1, n],
+ * out_bias [T].  fp32 throughout, products on the exact f32-input MFMA.  1 to SATRANS_MMOE_MAX_HIDDEN bottom layers, 0 to
+ * SATRANS_MMOE_MAX_HIDDEN tower layers; C and the widths are any positive integers.  Row tiles and weight-gradient chunks are
+ * those of the MMoE head (SATRANS_MMOE_ROW_TILE, SATRANS_MMOE_DW_ROW_CHUNK).
+ * The tower tail - the last tower layer, the final layer and out_bias - is ONE launch: a workgroup takes a row tile of a
+ * task's run, walks the 64-column tiles of the last tower layer, writes h = relu(acc + b) to saved and continues per row the
+ * chain logit = fmaf(h[n], tower_final_w[t][n], logit), n ascending from 0 over all tiles; logit + out_bias[t] is written.
+ * That is the arithmetic order of the tile product with one output column followed by its bias.  With n_tower = 0 the tail is
+ * the row-wise chain over the bottom's last rows.  satrans_sharedbottom_set_forward(1) makes the forward run the tail as those
+ * tile products instead (two launches, one with n_tower = 0), the form the tail was measured against
+ * (tools/sharedbottom_time.py): same bits in logit and saved.  0 is the fused tail.  Process-wide; returns the previous mode,
+ * or SATRANS_E_BADARG.
+ * saved: every hidden row in the caller's row order, the bottom's layers [B, n_l] first, then the tower's; the backward reads
+ * them.  The forward needs no workspace; the backward's holds two [B, widest row] dz buffers and the per-chunk partials of the
+ * weight gradients of the layer in hand (chunks counted from the start of a task's run for the towers, in the caller's row
+ * order for the bottom).  The tail's backward is pointwise, dz[row, n] = dlogit[row] tower_final_w[t][n] (h[row, n] > 0), and
+ * forms the chunk partials of d tower_final_w and d out_bias in the same pass.  The backward WRITES (does not accumulate) dx
+ * and every gradient of satrans_sharedbottom_grads, each of the shape of its parameter.  No floating-point atomics: chunks
+ * merge in chunk order, so equal inputs give equal bits and a task's rows give the same bits alone as inside a mixed batch
+ * (logit, dx, that task's tower, final-layer and out_bias gradients).  A task without rows gets zeros in its gradients. */
+typedef struct satrans_sharedbottom_desc {
+    int32_t B, C, T;
+    int32_t n_bottom, n_tower;              /* hidden layers of the two DNNs */
+    int32_t reserved;                       /* 0 */
+    int32_t bottom_width[SATRANS_MMOE_MAX_HIDDEN];
+    int32_t tower_width[SATRANS_MMOE_MAX_HIDDEN];
+    const float* x;
+    const int32_t *order, *seg;
+    const float* bottom_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* bottom_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* tower_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* tower_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* tower_final_w;
+    const float* out_bias;
+} satrans_sharedbottom_desc;
+typedef struct satrans_sharedbottom_grads {
+    float* bottom_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* bottom_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* tower_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* tower_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* tower_final_w;
+    float* out_bias;
+} satrans_sharedbottom_grads;
+int64_t satrans_sharedbottom_saved_floats(const satrans_sharedbottom_desc* d);
+int64_t satrans_sharedbottom_workspace_floats(const satrans_sharedbottom_desc* d);
+int satrans_sharedbottom_fwd(const satrans_sharedbottom_desc* d, float* logit, float* saved, void* stream);
+int satrans_sharedbottom_bwd(const satrans_sharedbottom_desc* d, const float* dlogit, float* dx, const float* saved,
+                             float* workspace, const satrans_sharedbottom_grads* g, void* stream);
+int satrans_sharedbottom_set_forward(int composed);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

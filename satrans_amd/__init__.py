@@ -5,8 +5,9 @@ from .callbacks import History  # noqa: F401
 from .basemodel import BaseModel  # noqa: F401
 from .satrans import SATrans  # noqa: F401
 from .layers import (AdaSparseHead, MDR_BatchNorm, MetaTransformation, MMoEHead, PartitionedNorm, PLEHead, PrunedDNN,  # noqa: F401
-                     SelfAttention_Layer, StarHead, StarTowers)
+                     SelfAttention_Layer, SharedBottomHead, StarHead, StarTowers)
 
 __all__ = ["SATrans", "BaseModel", "SparseFeat", "DenseFeat", "VarLenSparseFeat", "get_feature_names",
            "build_input_features", "History", "SelfAttention_Layer", "MetaTransformation",
-           "MDR_BatchNorm", "PartitionedNorm", "StarTowers", "StarHead", "MMoEHead", "PLEHead", "PrunedDNN", "AdaSparseHead"]
+           "MDR_BatchNorm", "PartitionedNorm", "StarTowers", "StarHead", "MMoEHead", "PLEHead", "PrunedDNN", "AdaSparseHead",
+           "SharedBottomHead"]

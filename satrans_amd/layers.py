@@ -920,6 +920,139 @@ class PLEHead(nn.Module):
         return logit
 
 
+def _sharedbottom_fill(tgt, cfg, tensors):
+    """Set the parameter pointers of a satrans_sharedbottom_desc / satrans_sharedbottom_grads from `tensors`, which hold, in the
+    order of N.SHAREDBOTTOM_POINTERS: bottom weights, bottom biases, tower weights, tower biases (stacked over the tasks), the
+    towers' final weight, the out biases."""
+    nb, nt = cfg
+    it = iter(tensors)
+    for name, per_layer in N.SHAREDBOTTOM_POINTERS:
+        if per_layer:
+            for l in range(nb if name.startswith("bottom") else nt):
+                getattr(tgt, name)[l] = next(it).data_ptr()
+        else:
+            setattr(tgt, name, next(it).data_ptr())
+    return tgt
+
+
+def _sharedbottom_desc(x, order, seg, cfg, tensors):
+    nb, nt = cfg
+    d = _sharedbottom_fill(N.SharedBottomDesc(), cfg, tensors)
+    d.B, d.C, d.T, d.n_bottom, d.n_tower = x.shape[0], x.shape[1], tensors[-1].shape[0], nb, nt
+    d.x, d.order, d.seg = x.data_ptr(), order.data_ptr(), seg.data_ptr()
+    for l in range(nb):
+        d.bottom_width[l] = tensors[l].shape[0]
+    for l in range(nt):
+        d.tower_width[l] = tensors[2 * nb + l].shape[1]
+    return d
+
+
+class _SharedBottomFn(torch.autograd.Function):
+    """logit [B,1] of the scenario-routed SharedBottom head (csrc/sharedbottom.hip); `tensors` as _sharedbottom_fill lists them."""
+
+    @staticmethod
+    def forward(ctx, x, order, seg, cfg, *tensors):
+        lib = N.lib()
+        dev = x.device
+        x = x.contiguous()
+        tensors = tuple(t.contiguous() for t in tensors)
+        d = _sharedbottom_desc(x, order, seg, cfg, tensors)
+        saved = torch.empty(_native_size(lib.satrans_sharedbottom_saved_floats, d), dtype=torch.float32, device=dev)
+        logit = torch.empty(x.shape[0], 1, dtype=torch.float32, device=dev)
+        N.check(lib.satrans_sharedbottom_fwd(C.byref(d), logit.data_ptr(), saved.data_ptr(), N.stream_handle(dev)),
+                "satrans_sharedbottom_fwd")
+        ctx.cfg = cfg
+        ctx.save_for_backward(x, order, seg, saved, *tensors)
+        ctx.mark_non_differentiable(saved)
+        return logit, saved
+
+    @staticmethod
+    def backward(ctx, dlogit, _dsaved):
+        lib = N.lib()
+        x, order, seg, saved, *tensors = ctx.saved_tensors
+        d = _sharedbottom_desc(x, order, seg, ctx.cfg, tensors)
+        work = torch.empty(_native_size(lib.satrans_sharedbottom_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        grads = [torch.empty_like(t) for t in tensors]
+        g = _sharedbottom_fill(N.SharedBottomGrads(), ctx.cfg, grads)
+        N.check(lib.satrans_sharedbottom_bwd(C.byref(d), dlogit.contiguous().data_ptr(), dx.data_ptr(), saved.data_ptr(),
+                                             work.data_ptr(), C.byref(g), N.stream_handle(x.device)), "satrans_sharedbottom_bwd")
+        return (dx, None, None, None, *grads)
+
+
+class SharedBottomHead(nn.Module):
+    """The bottom / tower half of the reference's SharedBottom.forward (models/sharedbottom.py:120-133) over a mixed batch, for
+    the reference's one-task-per-scenario use (T = tasks = scenarios): the loss of mtl_basemodel.py:268-269 and predict
+    (:376-378) read, of a row's T outputs, only the column of the row's own scenario.  So the bottom DNN runs over all rows, and
+    a row whose id is t + domain_id_offset goes through task t's tower DNN, tower_dnn_final_layer and out[t].bias - nothing of
+    the other tasks.
+
+    Parameter names, shapes, state_dict order and initialisation are the reference SharedBottom's (DNN weights N(0, init_std),
+    their biases and the bias-free final nn.Linears torch's default, out.{t}.bias zeros): out.{t}.bias,
+    bottom_dnn.linears.{l}.*, tower_dnn.{t}.linears.{l}.* (only with tower hidden units), tower_dnn_final_layer.{t}.weight -
+    those entries of a reference checkpoint load with load_state_dict.
+
+    forward(dnn_input [B, inputs_dim] fp32, domain_ids [B], domain_id_offset=0) -> logit [B,1]; the caller applies the
+    sigmoid.  Per call: the ids are bucketed once (one device-to-host read), the per-task parameters stacked (torch.stack;
+    autograd splits the gradients back), and one autograd.Function runs satrans_sharedbottom_fwd / satrans_sharedbottom_bwd.
+    `last_bottom` [B, last bottom width] is a view of the last forward's saved buffer: the shared bottom's output.
+
+    Differences from the reference.  (1) The module returns each row's OWN task logit, [B,1], not the [B,T] matrix of all
+    tasks: the other T - 1 columns are never computed.  (2) l2_reg_dnn is not applied (main.py leaves it 0).  (3) An id
+    outside [offset, offset + num_tasks) raises IndexError; the reference's loss silently leaves such rows out.
+    Not built - NotImplementedError at construction: an activation other than relu, dropout, batch-norm inside the DNNs,
+    no bottom layer, more than 3 hidden layers in a DNN."""
+
+    def __init__(self, inputs_dim, num_tasks, bottom_dnn_hidden_units=(256, 128), tower_dnn_hidden_units=(64,), init_std=0.0001,
+                 dnn_activation='relu', dnn_dropout=0, dnn_use_bn=False):
+        super().__init__()
+        if dnn_activation != 'relu':
+            raise NotImplementedError(f"SharedBottomHead: activation {dnn_activation!r} is not built (relu only)")
+        if dnn_dropout != 0:
+            raise NotImplementedError("SharedBottomHead: dropout inside the DNNs is not built (dnn_dropout must be 0)")
+        if dnn_use_bn:
+            raise NotImplementedError("SharedBottomHead: batch-norm inside the DNNs is not built (dnn_use_bn must be False)")
+        if num_tasks <= 1:
+            raise ValueError("num_tasks must be greater than 1")
+        bo, to = ([int(u) for u in units] for units in (bottom_dnn_hidden_units, tower_dnn_hidden_units))
+        if not 1 <= len(bo) <= N.MMOE_MAX_HIDDEN:
+            raise NotImplementedError(f"SharedBottomHead: 1 to {N.MMOE_MAX_HIDDEN} bottom hidden layers, got {len(bo)}")
+        if len(to) > N.MMOE_MAX_HIDDEN:
+            raise NotImplementedError(f"SharedBottomHead: 0 to {N.MMOE_MAX_HIDDEN} tower hidden layers, got {len(to)}")
+        if inputs_dim < 1 or min(bo + to) < 1:
+            raise ValueError("SharedBottomHead: inputs_dim and the hidden units must be positive")
+        self.inputs_dim, self.num_tasks = int(inputs_dim), int(num_tasks)
+        self.bottom_dnn_hidden_units, self.tower_dnn_hidden_units = tuple(bo), tuple(to)
+        T = self.num_tasks
+        # (first: in the reference's state_dict `out.*` precedes SharedBottom's own modules, because its BaseModel registers that name)
+        self.out = nn.ModuleList([_OutBias() for _ in range(T)])
+        self.bottom_dnn = _TowerDNN(inputs_dim, bo, init_std)
+        if to:
+            self.tower_dnn = nn.ModuleList([_TowerDNN(bo[-1], to, init_std) for _ in range(T)])
+        self.tower_dnn_final_layer = nn.ModuleList([nn.Linear(to[-1] if to else bo[-1], 1, bias=False) for _ in range(T)])
+        self.last_bottom = None
+
+    def forward(self, dnn_input, domain_ids, domain_id_offset=0):
+        x = dnn_input
+        if x.dim() != 2 or x.shape[1] != self.inputs_dim:
+            raise ValueError(f"SharedBottomHead: expected input [B, {self.inputs_dim}], got {tuple(x.shape)}")
+        N.require_gpu(x, "SharedBottomHead")
+        if x.dtype != torch.float32 or self.out[0].bias.dtype != torch.float32:
+            raise TypeError("SharedBottomHead: rows, parameters and gradients are float32")
+        order, seg, _ = _bucket_rows(x, domain_ids, self.num_tasks, domain_id_offset, "SharedBottomHead")
+        bo, nt = self.bottom_dnn_hidden_units, len(self.tower_dnn_hidden_units)
+        tensors = [m.weight for m in self.bottom_dnn.linears] + [m.bias for m in self.bottom_dnn.linears]
+        if nt:
+            layers = [[m.linears[l] for m in self.tower_dnn] for l in range(nt)]
+            tensors += ([torch.stack([m.weight for m in layer]) for layer in layers] +
+                        [torch.stack([m.bias for m in layer]) for layer in layers])
+        tensors += [torch.stack([m.weight for m in self.tower_dnn_final_layer]), torch.cat([m.bias for m in self.out])]
+        logit, saved = _SharedBottomFn.apply(x, order, seg, (len(bo), nt), *tensors)
+        B, at = x.shape[0], x.shape[0] * sum(bo[:-1])
+        self.last_bottom = saved[at:at + B * bo[-1]].view(B, bo[-1])
+        return logit
+
+
 def _adasparse_fill(tgt, L, tensors):
     """Set the parameter pointers of a satrans_adasparse_desc / satrans_adasparse_grads from `tensors`: L linears weights, L
     linears biases, L pruners weights, L pruners biases and, for the head, dnn_linear.weight and out.bias."""

@@ -171,6 +171,24 @@ class AdaSparseGrads(C.Structure):
     _fields_ = list(_ADASPARSE_POINTER_FIELDS)
 
 
+# the parameter pointers of satrans_sharedbottom_desc / satrans_sharedbottom_grads in the header's order: (name, per hidden layer)
+SHAREDBOTTOM_POINTERS = (("bottom_w", True), ("bottom_b", True), ("tower_w", True), ("tower_b", True), ("tower_final_w", False),
+                         ("out_bias", False))
+_SHAREDBOTTOM_POINTER_FIELDS = [(name, _vp * MMOE_MAX_HIDDEN if per_layer else _vp) for name, per_layer in SHAREDBOTTOM_POINTERS]
+
+
+class SharedBottomDesc(C.Structure):
+    """Mirror of `satrans_sharedbottom_desc` (row tile, chunk and layer limits are the MMoE head's: MMOE_*)."""
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("T", C.c_int32), ("n_bottom", C.c_int32), ("n_tower", C.c_int32),
+                ("reserved", C.c_int32), ("bottom_width", C.c_int32 * MMOE_MAX_HIDDEN), ("tower_width", C.c_int32 * MMOE_MAX_HIDDEN),
+                ("x", _vp), ("order", _vp), ("seg", _vp)] + _SHAREDBOTTOM_POINTER_FIELDS
+
+
+class SharedBottomGrads(C.Structure):
+    """Mirror of `satrans_sharedbottom_grads`."""
+    _fields_ = list(_SHAREDBOTTOM_POINTER_FIELDS)
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -278,6 +296,11 @@ SIGNATURES = {
     "satrans_adasparse_fwd": (C.c_int, [C.POINTER(AdaSparseDesc), _vp, _vp, _vp]),
     "satrans_adasparse_bwd": (C.c_int, [C.POINTER(AdaSparseDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(AdaSparseGrads), _vp]),
     "satrans_adasparse_set_forward": (C.c_int, [C.c_int]),
+    "satrans_sharedbottom_saved_floats": (C.c_int64, [C.POINTER(SharedBottomDesc)]),
+    "satrans_sharedbottom_workspace_floats": (C.c_int64, [C.POINTER(SharedBottomDesc)]),
+    "satrans_sharedbottom_fwd": (C.c_int, [C.POINTER(SharedBottomDesc), _vp, _vp, _vp]),
+    "satrans_sharedbottom_bwd": (C.c_int, [C.POINTER(SharedBottomDesc), _vp, _vp, _vp, _vp, C.POINTER(SharedBottomGrads), _vp]),
+    "satrans_sharedbottom_set_forward": (C.c_int, [C.c_int]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
