@@ -727,12 +727,16 @@ __device__ __forceinline__ void adam_step4(f32x2 (&p)[2], f32x2 (&m)[2], f32x2 (
 }
 
 // The same step in the FAST arithmetic (adam_core_fast, four elements): one path for every value - no range votes, no scaling.
+// The gradient is 2*l2*p as it is, without the `0 +` of the other forms: that sum only turns a -0 product into +0, and neither
+// sign of a zero gradient reaches a bit of m, v, p or the regulariser sum: (w2 g) g is +0 for either, and g - m differs (as -0
+// against +0) only under m = +0, where fma(w1, +-0, +0) is +0 (tests/test_lazy_uniform_loop_cpu.py holds the two spellings
+// against each other).
 __device__ __forceinline__ void adam_step4_fast(f32x2 (&p)[2], f32x2 (&m)[2], f32x2 (&v)[2], f32x2 (&sq)[2], float neg_step,
                                                 float rbc2f, const LazyK& k) {
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         sq[u] = pk_fma(p[u], p[u], sq[u]);
-        const f32x2 g = pk_add(pk_set(0.f), pk_mul(pk_set(k.l2x2), p[u]));
+        const f32x2 g = pk_mul(pk_set(k.l2x2), p[u]);
         m[u] = pk_fma(pk_set(k.w1), pk_sub(g, m[u]), m[u]);
         v[u] = pk_fma(pk_mul(pk_set(k.w2), g), g, pk_mul(v[u], pk_set(k.beta2)));
         const f32x2 a = pk_mul(pk_set(neg_step), m[u]);
@@ -743,18 +747,54 @@ __device__ __forceinline__ void adam_step4_fast(f32x2 (&p)[2], f32x2 (&m)[2], f3
     }
 }
 
-// four elements per lane; steps (from, to] ; table[s] = (lr / (1 - beta1^s) as fp32, 1 / (double)fp32(sqrt(1 - beta2^s))) as doubles
+// ---- the fast replay's step constants, once per workgroup --------------------------------------------------------------------
+// The fast step takes both constants of table[s] as fp32.  Converting them in the loop cost every lane two v_cvt_f32_f64 and a
+// 16-byte load through a per-lane address per step, with the wait for it inside the loop body.  A workgroup converts the steps
+// (target - kStagedSteps, target] once instead: s_steps[target - s] = {-(float)table[s].x, (float)table[s].y}.  Rows are at most
+// flush_every (32) steps behind with the periodic flush on; a wave with an older row takes the loop that reads the table.
+constexpr int kStagedSteps = 128;
+
+__device__ __forceinline__ void stage_steps(float2* s_steps, int target, const double2* __restrict__ table) {
+    const int s = target - (int)threadIdx.x;
+    if (threadIdx.x < kStagedSteps && s >= 1) {
+        const double2 hp = table[s];
+        s_steps[threadIdx.x] = make_float2(-(float)hp.x, (float)hp.y);
+    }
+    __syncthreads();
+}
+
+// smallest `x` of the wave, in a scalar register; every lane of the wave must be here
+__device__ __forceinline__ int wave_min(int x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x = min(x, __shfl_xor(x, off));
+    return __builtin_amdgcn_readfirstlane(x);
+}
+
+// four elements per lane; steps (from, to] ; table[s] = (lr / (1 - beta1^s) as fp32, 1 / (double)fp32(sqrt(1 - beta2^s))) as doubles.
+// Called by EVERY lane of a wave (a lane without work passes from = to), `s_steps` as stage_steps left it for target = to.
 __device__ __forceinline__ double replay_element4(float4& P4, float4& M4, float4& V4, int from, int to,
-                                                  const double2* __restrict__ table, const LazyK& k) {
+                                                  const double2* __restrict__ table, const float2* s_steps, const LazyK& k) {
     // sum of p^2 over the replayed steps in fp32 (<= a few thousand terms of one element: relative error ~1e-7 x steps,
     // far inside the fp32 reduction the reference itself uses), converted to double once; the sums over elements,
     // blocks and steps stay in double
     f32x2 p[2] = {{P4.x, P4.y}, {P4.z, P4.w}}, m[2] = {{M4.x, M4.y}, {M4.z, M4.w}}, v[2] = {{V4.x, V4.y}, {V4.z, V4.w}};
     f32x2 sq[2] = {{0.f, 0.f}, {0.f, 0.f}};
     if (k.fast) {
-        for (int s = from + 1; s <= to; ++s) {
-            const double2 hp = table[s];
-            adam_step4_fast(p, m, v, sq, -(float)hp.x, (float)hp.y, k);
+        // All lanes end at `to`; only `from` differs.  So the wave runs ONE loop with a scalar counter, from its smallest
+        // from + 1, and a lane joins when the counter has passed its own `from`: each lane still takes exactly its own steps, in
+        // order.  The constants of a step are one LDS read at a uniform address, fetched a step ahead and moved to scalar
+        // registers, where the packed instructions take them as operands.
+        const int first = wave_min(from) + 1;
+        if (first >= 1 && to - first < kStagedSteps) {
+            for (int s = first; s <= to; ++s) {
+                const float2 c = s_steps[to - s];
+                if (s > from) adam_step4_fast(p, m, v, sq, c.x, c.y, k);
+            }
+        } else {
+            for (int s = from + 1; s <= to; ++s) {
+                const double2 hp = table[s];
+                adam_step4_fast(p, m, v, sq, -(float)hp.x, (float)hp.y, k);
+            }
         }
     } else {
         for (int s = from + 1; s <= to; ++s) {
@@ -777,22 +817,26 @@ __global__ __launch_bounds__(256) void lazy_replay_kernel(float4* __restrict__ P
                                                          double* __restrict__ reg_partials, int64_t slots) {
     constexpr int LR = D / 4;
     __shared__ double s_red[256];
+    __shared__ float2 s_steps[kStagedSteps];
+    if (k.fast) stage_steps(s_steps, target, table);
     const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LR;
     const int c = threadIdx.x % LR;
-    double reg = 0.0;
+    // (a lane without work goes through the replay with nothing to do: the fast loop is the wave's, not the lane's)
+    int from = target;
+    int64_t at = 0;
     if (j < n) {
         const int32_t row = sorted_rows[j];
         const bool head = j == 0 || sorted_rows[j - 1] != row;
         if (head) {
-            const int from = last[row];
-            if (from < target) {
-                const int64_t at = (int64_t)row * LR + c;
-                float4 p = P[at], m = M[at], v = V[at];
-                reg = replay_element4(p, m, v, from, target, table, k);
-                P[at] = p; M[at] = m; V[at] = v;
-            }
+            from = min(last[row], target);
+            at = (int64_t)row * LR + c;
         }
     }
+    const bool work = from < target;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), m = p, v = p;
+    if (work) { p = P[at]; m = M[at]; v = V[at]; }
+    const double reg = replay_element4(p, m, v, from, target, table, s_steps, k);
+    if (work) { P[at] = p; M[at] = m; V[at] = v; }
     // every lane of a row has read last[row] before any lane overwrites it
     __syncthreads();
     if (j < n && c == 0) {
@@ -814,17 +858,22 @@ __global__ __launch_bounds__(256) void lazy_flush_kernel(float4* __restrict__ P,
                                                         double* __restrict__ reg_partials) {
     constexpr int LR = D / 4;
     __shared__ double s_red[256];
+    __shared__ float2 s_steps[kStagedSteps];
+    if (k.fast) stage_steps(s_steps, target, table);
     double reg = 0.0;
     const int64_t groups_per_pass = (int64_t)gridDim.x * 256 / LR;
     const int c = threadIdx.x % LR;
-    for (int64_t row = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LR; row < total_rows; row += groups_per_pass) {
-        const int from = last[row];
-        if (from < target) {
-            const int64_t at = row * LR + c;
-            float4 p = P[at], m = M[at], v = V[at];
-            reg += replay_element4(p, m, v, from, target, table, k);
-            P[at] = p; M[at] = m; V[at] = v;
-        }
+    // the trip count is the wave's (its first row decides), so that every lane of it is there for the fast loop
+    const int first_lane = (int)(threadIdx.x & ~63u);
+    for (int64_t row0 = ((int64_t)blockIdx.x * 256 + first_lane) / LR; row0 < total_rows; row0 += groups_per_pass) {
+        const int64_t row = row0 + (threadIdx.x - first_lane) / LR;
+        const int from = row < total_rows ? min(last[row], target) : target;
+        const bool work = from < target;
+        const int64_t at = row * LR + c;
+        float4 p = make_float4(0.f, 0.f, 0.f, 0.f), m = p, v = p;
+        if (work) { p = P[at]; m = M[at]; v = V[at]; }
+        reg += replay_element4(p, m, v, from, target, table, s_steps, k);
+        if (work) { P[at] = p; M[at] = m; V[at] = v; }
     }
     __syncthreads();    // all reads of last[] in this block are done; blocks own disjoint rows
     for (int64_t row = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LR; row < total_rows; row += groups_per_pass)
