@@ -1,6 +1,8 @@
-// The grouped 64 x 64 tile product of the scenario heads (mmoe.hip, ple.hip), its weight-gradient and reduce kernels, and the
-// softmax mixture over up to 8 experts.  Every kernel sits in an unnamed namespace: each file that includes this header gets
-// its own copies, under the names mmoe.hip gave them.  star.hip keeps its own tile product (with the shared factor).
+// The grouped 64 x 64 tile product of the scenario heads (mmoe.hip, ple.hip, sharedbottom.hip, adasparse.hip) and of STAR's
+// towers (star.hip), its weight-gradient and reduce kernels, and the softmax mixture over up to 8 experts.  Every kernel sits
+// in an unnamed namespace: each file that includes this header gets its own copies, under the names mmoe.hip gave them.
+// star.hip wraps the same tile body with the shared factor switched on (SHARED: W_dom * W_sh on operand load, b_dom + b_sh)
+// and the weight-gradient body with G = 1 as a constant.
 //
 // Layout.  Rows, hidden rows, dz and dx stay in the caller's row order.  The hidden rows of G blocks of a layer sit side by
 // side: [B, G * n_l], block g in columns [g n_l, (g + 1) n_l).  A workgroup owns (one row tile of kTM rows) x (one tile of kTN
@@ -65,18 +67,17 @@ __device__ __forceinline__ int unit_row(const int32_t* __restrict__ order, int p
 // ---- forward layers and the input gradients -------------------------------------------------------------------------------------
 
 // group of the workgroup: block g of G (dense) or block g of G of the rows' task t (ROUTED; G = 1: the task's whole rows).
-// W = w + g N K (dense) or w + (t G + g) N K (ROUTED), row strides ldin / ldout:
+// W = w + g N K (dense) or w + (t G + g) N K (ROUTED), times w_sh [N, K] elementwise when SHARED; row strides ldin / ldout:
 //   out[row, g ogo + n] = epilogue(sum_k in[row, g igo + k] * W[n, k])            WT = false   (W [N, K])
 //   out[row, g ogo + n] = epilogue(sum_k in[row, g igo + k] * W[k, n])            WT = true    (W [K, N])
-// epilogue: + bias[group N + n] (when bias), relu (when relu), * (mask[same place as out] > 0) (when mask), + out (when add)
-// grid: ROUTED  row-tile slots x G x n tiles;  dense  row tiles x G x n tiles
-template <bool WT, bool ROUTED>
-__global__ __launch_bounds__(kThreads) void mmoe_gemm_kernel(const float* __restrict__ in, int ldin, int igo,
-                                                             const int32_t* __restrict__ order, const int32_t* __restrict__ seg,
-                                                             int B, int K, int N, int S, int G, int ntiles,
-                                                             const float* __restrict__ w, const float* __restrict__ bias, int relu,
-                                                             const float* __restrict__ mask, int add, float* out, int ldout,
-                                                             int ogo) {
+// epilogue: + bias[group N + n] (+ b_sh[n] when SHARED) (when bias), relu (when relu), * (mask[same place as out] > 0) (when
+// mask), + out (when add)
+template <bool WT, bool ROUTED, bool SHARED>
+__device__ __forceinline__ void gemm_tile(const float* __restrict__ in, int ldin, int igo, const int32_t* __restrict__ order,
+                                          const int32_t* __restrict__ seg, int B, int K, int N, int S, int G, int ntiles,
+                                          const float* __restrict__ w, const float* __restrict__ w_sh,
+                                          const float* __restrict__ bias, const float* __restrict__ b_sh, int relu,
+                                          const float* __restrict__ mask, int add, float* out, int ldout, int ogo) {
     __shared__ float As[kTM][kLd];
     __shared__ float Bs[kTN][kLd];
     __shared__ int rows_sh[kTM];
@@ -115,7 +116,10 @@ __global__ __launch_bounds__(kThreads) void mmoe_gemm_kernel(const float* __rest
                 ok = n < N && k < K;
                 at = (size_t)n * K + k;
             }
-            rb[e] = ok ? wd[at] : 0.f;
+            if (SHARED)
+                rb[e] = ok ? wd[at] * w_sh[at] : 0.f;
+            else
+                rb[e] = ok ? wd[at] : 0.f;
         }
     };
     f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -136,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void mmoe_gemm_kernel(const float* __rest
     }
     const int n = n0 + wn * 32 + (lane & 31);
     if (n >= N) return;
-    const float bv = bias ? bias[grp * N + n] : 0.f;
+    const float bv = bias ? (SHARED ? bias[grp * N + n] + b_sh[n] : bias[grp * N + n]) : 0.f;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         const int row = rows_sh[wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)];
@@ -148,6 +152,18 @@ __global__ __launch_bounds__(kThreads) void mmoe_gemm_kernel(const float* __rest
         if (add) v = out[at] + v;
         out[at] = v;
     }
+}
+
+// grid: ROUTED  row-tile slots x G x n tiles;  dense  row tiles x G x n tiles
+template <bool WT, bool ROUTED>
+__global__ __launch_bounds__(kThreads) void mmoe_gemm_kernel(const float* __restrict__ in, int ldin, int igo,
+                                                             const int32_t* __restrict__ order, const int32_t* __restrict__ seg,
+                                                             int B, int K, int N, int S, int G, int ntiles,
+                                                             const float* __restrict__ w, const float* __restrict__ bias, int relu,
+                                                             const float* __restrict__ mask, int add, float* out, int ldout,
+                                                             int ogo) {
+    gemm_tile<WT, ROUTED, false>(in, ldin, igo, order, seg, B, K, N, S, G, ntiles, w, nullptr, bias, nullptr, relu, mask, add, out,
+                                 ldout, ogo);
 }
 
 // ---- softmax and mixture --------------------------------------------------------------------------------------------------------
@@ -227,11 +243,9 @@ __global__ __launch_bounds__(kThreads) void mmoe_mix_bwd_kernel(const float* __r
 // part_b[u][n] = sum of dz[row, g zgo + n] (when part_b).  ROUTED: u = chunk slot * G + g (the slot names the task).
 // Dense: u = chunk * G + g.   grid: units x n tiles x k tiles
 template <bool ROUTED>
-__global__ __launch_bounds__(kThreads) void mmoe_dw_kernel(const float* __restrict__ dz, int ldz, int zgo, const float* __restrict__ h,
-                                                           int ldh, int hgo, const int32_t* __restrict__ order,
-                                                           const int32_t* __restrict__ seg, int B, int K, int N, int S, int G,
-                                                           int ntiles, int ktiles, float* __restrict__ part_w,
-                                                           float* __restrict__ part_b) {
+__device__ __forceinline__ void dw_tile(const float* __restrict__ dz, int ldz, int zgo, const float* __restrict__ h, int ldh, int hgo,
+                                        const int32_t* __restrict__ order, const int32_t* __restrict__ seg, int B, int K, int N, int S,
+                                        int G, int ntiles, int ktiles, float* __restrict__ part_w, float* __restrict__ part_b) {
     __shared__ float As[kTM][kLd];      // [n][row of the step]
     __shared__ float Bs[kTN][kLd];      // [k][row of the step]
     const int per_unit = ntiles * ktiles;
@@ -280,6 +294,15 @@ __global__ __launch_bounds__(kThreads) void mmoe_dw_kernel(const float* __restri
         const int n = n0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
         if (n < N) out[(size_t)n * K + c] = acc[q];
     }
+}
+
+template <bool ROUTED>
+__global__ __launch_bounds__(kThreads) void mmoe_dw_kernel(const float* __restrict__ dz, int ldz, int zgo, const float* __restrict__ h,
+                                                           int ldh, int hgo, const int32_t* __restrict__ order,
+                                                           const int32_t* __restrict__ seg, int B, int K, int N, int S, int G,
+                                                           int ntiles, int ktiles, float* __restrict__ part_w,
+                                                           float* __restrict__ part_b) {
+    dw_tile<ROUTED>(dz, ldz, zgo, h, ldh, hgo, order, seg, B, K, N, S, G, ntiles, ktiles, part_w, part_b);
 }
 
 // One thread per element of a group's [N*K weights | N biases] (the biases only when part_b): the group's chunks in chunk

@@ -5,11 +5,11 @@
 // tiles of kTM rows (products) or chunks of kDwChunk rows (weight gradients) and the grids are sized in slots, as seg_walk.h
 // describes.  A workgroup owns (one row tile) x (one tile of kTN output columns) and streams the contraction in steps of kTK.
 //
-// Products.  Exact f32-input MFMA (v_mfma_f32_32x32x2_f32): a result element is a k-ordered fmaf chain, so it does not depend on
-// the tile a row falls into.  The four waves of a workgroup take the 2 x 2 quadrants of its 64 x 64 tile, one 32 x 32
-// accumulator each.  Both operands go through LDS ([64][kTK + 1] floats, conflict-free for the fragment reads); the next step's
-// global loads are issued before the current step's MFMAs.  W_eff is never materialised: the weight tile is W_dom * W_sh,
-// multiplied on its way into LDS (both L2-resident; at S = 32 a materialised W_eff would be another 24 MB written and read).
+// Products.  The tile product and the weight-gradient body are those of grouped_gemm.h, shared with the scenario heads: exact
+// f32-input MFMA, a result element is a k-ordered fmaf chain, so it does not depend on the tile a row falls into.  This file
+// holds the reduction (which folds in W_sh and the sum over scenarios), the layout, the validation and the launches.  W_eff is
+// never materialised: the weight tile is W_dom * W_sh, multiplied on its way into LDS (the SHARED form of the tile body; both
+// L2-resident; at S = 32 a materialised W_eff would be another 24 MB written and read).
 //
 //   forward   h_l = relu(h_{l-1} W_eff^T + b_eff), every layer one launch of star_gemm_kernel<false>; the last layer (width 1) is
 //             the same kernel with one valid column.  h_1 .. h_{L-1} are SAVED (row order) for the backward.
@@ -22,169 +22,36 @@
 // No floating-point atomics anywhere: equal inputs give equal bits, and a scenario's rows give the same bits alone as in a mix.
 #include <algorithm>
 
-#include "seg_walk.h"
+#include "grouped_gemm.h"
 
 namespace satrans {
 namespace {
 
-constexpr int kTM = SATRANS_STAR_ROW_TILE;
-constexpr int kTN = 64;
-constexpr int kTK = 32;
-constexpr int kLd = kTK + 1;
-constexpr int kThreads = 256;
-constexpr int kDwChunk = SATRANS_STAR_DW_ROW_CHUNK;
-constexpr int kPer = kTM * kTK / kThreads;      // elements of an operand tile per thread
-static_assert(kTM == 64 && kTN == 64, "four waves take the 2 x 2 quadrants of 32 x 32");
-static_assert(kDwChunk % kTK == 0 && kPer == 8, "tile loaders");
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// one contraction step of the workgroup's 64 x 64 tile: wave quadrant (wm, wn), A[i][k] = As[i][k], B[k][j] = Bs[j][k]
-__device__ __forceinline__ void mma_step(const float (*As)[kLd], const float (*Bs)[kLd], int lane, int wm, int wn, f32x16& acc) {
-    const int r = lane & 31, h = lane >> 5;
-    const float* a = &As[wm * 32 + r][h];
-    const float* b = &Bs[wn * 32 + r][h];
-#pragma unroll
-    for (int kk = 0; kk < kTK; kk += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], b[kk], acc, 0, 0, 0);
-}
-
-// Thread mappings of a [64][kTK] operand tile, element e = 0..kPer-1 of thread t:
-//   "k fast"  (the contraction index is contiguous in memory):  i = (t >> 5) + 8 e,  k = t & 31
-//   "i fast"  (the tile's row index is contiguous in memory):   i = t & 63,          k = (t >> 6) + 4 e
-
-// ---- forward layers and the input gradients -------------------------------------------------------------------------------------
+static_assert(SATRANS_STAR_ROW_TILE == SATRANS_MMOE_ROW_TILE && SATRANS_STAR_DW_ROW_CHUNK == SATRANS_MMOE_DW_ROW_CHUNK,
+              "STAR's row tile and weight-gradient chunk are those of grouped_gemm.h");
 
 // out[row, n] = epilogue(sum_k in[row, k] * Weff[s][n, k])                     WT = false   (W [N, K] per scenario)
 // out[row, n] = epilogue(sum_k in[row, k] * Weff[s][k, n])                     WT = true    (W [K, N] per scenario)
 // epilogue: + b_dom[s][n] + b_sh[n] (when b_dom), relu (when relu), * (mask[row, n] > 0) (when mask)
+// grid: row-tile slots x n tiles
 template <bool WT>
 __global__ __launch_bounds__(kThreads) void star_gemm_kernel(const float* __restrict__ in, const int32_t* __restrict__ order,
                                                              const int32_t* __restrict__ seg, int B, int K, int N, int S, int ntiles,
                                                              const float* __restrict__ w_dom, const float* __restrict__ w_sh,
                                                              const float* __restrict__ b_dom, const float* __restrict__ b_sh,
                                                              int relu, const float* __restrict__ mask, float* __restrict__ out) {
-    __shared__ float As[kTM][kLd];
-    __shared__ float Bs[kTN][kLd];
-    __shared__ int rows_sh[kTM];
-    const int slot = blockIdx.x / ntiles, n0 = (blockIdx.x % ntiles) * kTN;
-    const SegSlot tl = find_slot<SegSlot>(seg, S, B, slot, kTM);
-    if (tl.s < 0) return;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w & 1, wn = w >> 1;
-    if (t < kTM) rows_sh[t] = row_at(order, tl.r0 + t, tl.r1, B);
-    const float* wd = w_dom + (size_t)tl.s * N * K;
-    const int kf = t & 31, if0 = t >> 5;      // "k fast"
-    const int jf = t & 63, kf0 = t >> 6;      // "i fast"
-    int my_rows[kPer];
-#pragma unroll
-    for (int e = 0; e < kPer; ++e) my_rows[e] = row_at(order, tl.r0 + if0 + 8 * e, tl.r1, B);
-    float ra[kPer], rb[kPer];
-    auto load = [&](int k0) {
-#pragma unroll
-        for (int e = 0; e < kPer; ++e) {
-            const int k = k0 + kf;
-            ra[e] = (my_rows[e] >= 0 && k < K) ? in[(size_t)my_rows[e] * K + k] : 0.f;
-        }
-#pragma unroll
-        for (int e = 0; e < kPer; ++e) {
-            size_t at;
-            bool ok;
-            if (WT) {
-                const int n = n0 + jf, k = k0 + kf0 + 4 * e;
-                ok = n < N && k < K;
-                at = (size_t)k * N + n;
-            } else {
-                const int n = n0 + if0 + 8 * e, k = k0 + kf;
-                ok = n < N && k < K;
-                at = (size_t)n * K + k;
-            }
-            rb[e] = ok ? wd[at] * w_sh[at] : 0.f;
-        }
-    };
-    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    load(0);
-    for (int k0 = 0; k0 < K; k0 += kTK) {
-        __syncthreads();      // the previous step's fragment reads are done
-#pragma unroll
-        for (int e = 0; e < kPer; ++e) {
-            As[if0 + 8 * e][kf] = ra[e];
-            if (WT)
-                Bs[jf][kf0 + 4 * e] = rb[e];
-            else
-                Bs[if0 + 8 * e][kf] = rb[e];
-        }
-        __syncthreads();
-        if (k0 + kTK < K) load(k0 + kTK);
-        mma_step(As, Bs, lane, wm, wn, acc);
-    }
-    const int n = n0 + wn * 32 + (lane & 31);
-    if (n >= N) return;
-    const float bias = b_dom ? b_dom[(size_t)tl.s * N + n] + b_sh[n] : 0.f;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int row = rows_sh[wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)];
-        if (row < 0) continue;
-        float v = acc[q] + bias;
-        if (relu) v = fmaxf(v, 0.f);
-        const size_t at = (size_t)row * N + n;
-        if (mask) v = mask[at] > 0.f ? v : 0.f;
-        out[at] = v;
-    }
+    gemm_tile<WT, /*ROUTED=*/true, /*SHARED=*/true>(in, K, 0, order, seg, B, K, N, S, 1, ntiles, w_dom, w_sh, b_dom, b_sh, relu, mask, 0,
+                                                    out, N, 0);
 }
 
-// ---- weight gradients -----------------------------------------------------------------------------------------------------------
-
 // part_w[chunk][n, k] = sum over the chunk's rows of dz[row, n] * h[row, k];  part_b[chunk][n] = sum of dz[row, n]
-// grid: chunk slots x n tiles x k tiles
+// grid: chunk slots x n tiles x k tiles.  The routed body of mmoe_dw_kernel with G = 1 and whole rows as constants: a workgroup
+// runs only eight steps, so the two divisions by a runtime G in front of them would show (1 % of forward + backward at S = 32).
 __global__ __launch_bounds__(kThreads) void star_dw_kernel(const float* __restrict__ dz, const float* __restrict__ h,
                                                            const int32_t* __restrict__ order, const int32_t* __restrict__ seg, int B,
                                                            int K, int N, int S, int ntiles, int ktiles, float* __restrict__ part_w,
                                                            float* __restrict__ part_b) {
-    __shared__ float As[kTM][kLd];      // [n][row of the step]
-    __shared__ float Bs[kTN][kLd];      // [k][row of the step]
-    const int per_slot = ntiles * ktiles;
-    const int slot = blockIdx.x / per_slot, rem = blockIdx.x % per_slot;
-    const int n0 = (rem / ktiles) * kTM, c0 = (rem % ktiles) * kTN;
-    const SegSlot tl = find_slot<SegSlot>(seg, S, B, slot, kDwChunk);
-    if (tl.s < 0) return;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6, wm = w & 1, wn = w >> 1;
-    const int jf = t & 63, kf0 = t >> 6;
-    float ra[kPer], rb[kPer];
-    auto load = [&](int p0) {
-#pragma unroll
-        for (int e = 0; e < kPer; ++e) {
-            const int row = row_at(order, p0 + kf0 + 4 * e, tl.r1, B);
-            const int n = n0 + jf, c = c0 + jf;
-            ra[e] = (row >= 0 && n < N) ? dz[(size_t)row * N + n] : 0.f;
-            rb[e] = (row >= 0 && c < K) ? h[(size_t)row * K + c] : 0.f;
-        }
-    };
-    f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float bsum = 0.f;
-    load(tl.r0);
-    for (int p0 = tl.r0; p0 < tl.r1; p0 += kTK) {
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < kPer; ++e) {
-            As[jf][kf0 + 4 * e] = ra[e];
-            Bs[jf][kf0 + 4 * e] = rb[e];
-        }
-        __syncthreads();
-        if (p0 + kTK < tl.r1) load(p0 + kTK);
-        if (c0 == 0 && t < kTM) {      // the bias gradient: rows of the chunk in order (rows past its end hold zeros)
-#pragma unroll
-            for (int kk = 0; kk < kTK; ++kk) bsum += As[t][kk];
-        }
-        mma_step(As, Bs, lane, wm, wn, acc);
-    }
-    if (c0 == 0 && t < kTM && n0 + t < N) part_b[(size_t)slot * N + n0 + t] = bsum;
-    const int c = c0 + wn * 32 + (lane & 31);
-    if (c >= K) return;
-    float* out = part_w + (size_t)slot * N * K;
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int n = n0 + wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5);
-        if (n < N) out[(size_t)n * K + c] = acc[q];
-    }
+    dw_tile<true>(dz, N, 0, h, K, 0, order, seg, B, K, N, S, 1, ntiles, ktiles, part_w, part_b);
 }
 
 // One thread per element of [N*K weights | N biases]: the chunks of a scenario in chunk order, the scenarios in scenario order.
