@@ -9,9 +9,9 @@
 //                                             through LDS once per contraction step and feeds two weight tiles and two MFMA
 //                                             accumulators; whole steps past K skip the fc product; the epilogue writes pi,
 //                                             dzf = d(fc pi)/dz and h' into `saved`
-//             mmoe_gemm_kernel<false, false>  logit = h_L w^T + out_bias (the plain tile product with N = 1)
-//   backward  the logit layer as the other heads do it (mmoe_dw_kernel, mmoe_reduce_kernel, mmoe_gemm_kernel<true, false> with
-//             the relu mask of h_L), then per layer, last to first:
+//             mmoe_gemm_kernel<false, false>  logit = h_L w^T + out_bias (head_layers.h's launch_fwd<false>, a layer with N = 1)
+//   backward  the logit layer as the other heads do it (head_layers.h's launch_bwd<false>: mmoe_dw_kernel, mmoe_reduce_kernel,
+//             mmoe_gemm_kernel<true, false> with the relu mask of h_L), then per layer, last to first:
 //             ada_dd_kernel                   [dfc | dz] = [g pi | g dzf] [B, 2N] from the masked output gradient g
 //             ada_dw_kernel                   partials of dW = dfc^T h and dP = dz^T [h | e] over chunks of kDwChunk rows: the
 //                                             [h | e] tile is staged once and feeds both; the column blocks past K come from e and
@@ -25,9 +25,7 @@
 //
 // satrans_adasparse_set_forward(1) swaps the fused forward layer for the composed form it was measured against: the fc product,
 // a concatenating copy, the z product over the copy, and a pointwise epilogue (tools/adasparse_time.py).
-#include <algorithm>
-
-#include "grouped_gemm.h"
+#include "head_layers.h"
 
 namespace satrans {
 namespace {
@@ -307,7 +305,7 @@ __global__ __launch_bounds__(kThreads) void ada_din_kernel(const float* __restri
 struct AdaLayout {
     int nl;
     int K[kMaxH], N[kMaxH];
-    int64_t tiles, chunks;
+    Rows rows;      // nothing is routed: T = 0, no order, no seg
     int64_t s_pi[kMaxH], s_fc[kMaxH], s_h[kMaxH], s_cat, saved;      // floats from the start of saved (s_fc: dzf)
     int64_t max_w, w_g, w_dd, w_part, total;                         // workspace
 };
@@ -324,16 +322,15 @@ int ada_validate(const satrans_adasparse_desc* d, const char* who, AdaLayout& L)
                     (double)d->epsilon);
     const int64_t B = d->B, E = d->E;
     L.nl = d->n_layers;
-    L.tiles = ceil_div(B, kTM);
-    L.chunks = ceil_div(B, kDwChunk);
+    L.rows = rows_of(d->B, 0, nullptr, nullptr);
     int64_t at = 0, per_part = 0, max_ke = 0;
     L.max_w = 1;
     int prev = d->C;
     for (int l = 0; l < L.nl; ++l) {
         const int64_t K = prev, N = d->width[l], KE = K + E;
         SATRANS_REQUIRE(KE <= 0x7fffffffLL / 4 && N <= 0x7fffffffLL / 8 && N * KE <= 0x7fffffffLL &&
-                            L.tiles * ceil_div(std::max(N, KE), kTN) <= 0x7fffffffLL &&
-                            L.chunks * ceil_div(N, kTM) * ceil_div(KE, kTN) <= 0x7fffffffLL,
+                            L.rows.tiles * ceil_div(std::max(N, KE), kTN) <= 0x7fffffffLL &&
+                            L.rows.chunks * ceil_div(N, kTM) * ceil_div(KE, kTN) <= 0x7fffffffLL,
                         SATRANS_E_UNSUPPORTED, "%s: layer %d (%lld x %lld) at B=%d needs more than 2^31 workgroups", who, l, (long long)N,
                         (long long)KE, d->B);
         L.K[l] = (int)K, L.N[l] = (int)N;
@@ -341,10 +338,10 @@ int ada_validate(const satrans_adasparse_desc* d, const char* who, AdaLayout& L)
         at += 3 * B * N;
         L.max_w = std::max(L.max_w, N);
         max_ke = std::max(max_ke, KE);
-        per_part = std::max(per_part, L.chunks * (N * (K + 1) + N * (KE + 1)));
+        per_part = std::max(per_part, L.rows.chunks * (N * (K + 1) + N * (KE + 1)));
         prev = (int)N;
     }
-    per_part = std::max(per_part, L.chunks * ((int64_t)prev + 1));      // the logit layer
+    per_part = std::max(per_part, L.rows.chunks * ((int64_t)prev + 1));      // the logit layer
     L.s_cat = at;
     if (g_composed) at += B * max_ke;
     L.saved = at;
@@ -367,15 +364,6 @@ bool ada_has_grads(const satrans_adasparse_desc* d, const satrans_adasparse_grad
     for (int l = 0; l < d->n_layers; ++l)
         if (!g->lin_w[l] || !g->lin_b[l] || !g->prn_w[l] || !g->prn_b[l]) return false;
     return true;
-}
-
-// out [B, N] = in [B, K] w^T (+ bias) with the plain dense tile product
-int launch_plain(const AdaLayout& L, const float* in, int B, int K, int N, const float* w, const float* bias, float* out, hipStream_t st) {
-    const int ntiles = (int)ceil_div(N, kTN);
-    mmoe_gemm_kernel<false, false><<<(unsigned)(L.tiles * ntiles), kThreads, 0, st>>>(in, K, 0, nullptr, nullptr, B, K, N, 0, 1, ntiles, w,
-                                                                                     bias, 0, nullptr, 0, out, N, 0);
-    SATRANS_CHECK_LAUNCH("mmoe_gemm_kernel (adasparse forward)");
-    return SATRANS_OK;
 }
 
 }  // namespace
@@ -416,23 +404,26 @@ extern "C" int satrans_adasparse_fwd(const satrans_adasparse_desc* d, float* log
         if (g_composed) {
             float* cat = saved + L.s_cat;
             const int64_t nc = (int64_t)B * (K + E), no = (int64_t)B * N;
-            if ((rc = launch_plain(L, in, B, K, N, d->lin_w[l], d->lin_b[l], fc, st))) return rc;
+            const Lyr lin{K, N, 1, d->lin_w[l], d->lin_b[l], nullptr, nullptr};
+            const Lyr prn{K + E, N, 1, d->prn_w[l], d->prn_b[l], nullptr, nullptr};
+            if ((rc = launch_fwd<false>(L.rows, lin, in, K, 0, 0, fc, N, 0, st))) return rc;
             ada_cat_kernel<<<(unsigned)ceil_div(nc, kThreads), kThreads, 0, st>>>(in, d->emb, nc, K, E, cat);
             SATRANS_CHECK_LAUNCH("ada_cat_kernel");
-            if ((rc = launch_plain(L, cat, B, K + E, N, d->prn_w[l], d->prn_b[l], pi, st))) return rc;
+            if ((rc = launch_fwd<false>(L.rows, prn, cat, K + E, 0, 0, pi, N, 0, st))) return rc;
             ada_epilogue_kernel<<<(unsigned)ceil_div(no, kThreads), kThreads, 0, st>>>(fc, pi, no, d->alpha, d->beta, d->epsilon, out);
             SATRANS_CHECK_LAUNCH("ada_epilogue_kernel");
         } else {
             const int ntiles = (int)ceil_div(N, kTN);
-            ada_fwd_kernel<<<(unsigned)(L.tiles * ntiles), kThreads, 0, st>>>(in, d->emb, B, K, E, N, ntiles, d->lin_w[l], d->lin_b[l],
-                                                                             d->prn_w[l], d->prn_b[l], d->alpha, d->beta, d->epsilon, pi,
-                                                                             fc, out);
+            ada_fwd_kernel<<<(unsigned)(L.rows.tiles * ntiles), kThreads, 0, st>>>(in, d->emb, B, K, E, N, ntiles, d->lin_w[l],
+                                                                                  d->lin_b[l], d->prn_w[l], d->prn_b[l], d->alpha, d->beta,
+                                                                                  d->epsilon, pi, fc, out);
             SATRANS_CHECK_LAUNCH("ada_fwd_kernel");
         }
         in = out;
     }
     if (!d->final_w) return SATRANS_OK;      // the DNN alone: h_L is the last block of saved
-    return launch_plain(L, in, B, L.N[L.nl - 1], 1, d->final_w, d->out_bias, logit, st);
+    const Lyr fin{L.N[L.nl - 1], 1, 1, d->final_w, d->out_bias, nullptr, nullptr};
+    return launch_fwd<false>(L.rows, fin, in, fin.K, 0, 0, logit, 1, 0, st);
 }
 
 extern "C" int satrans_adasparse_bwd(const satrans_adasparse_desc* d, const float* dlogit, float* dx, float* demb, const float* saved,
@@ -443,26 +434,15 @@ extern "C" int satrans_adasparse_bwd(const satrans_adasparse_desc* d, const floa
     if (rc) return rc;
     SATRANS_REQUIRE(ada_has_operands(d) && dlogit && dx && demb && saved && workspace && ada_has_grads(d, g), SATRANS_E_BADARG,
                     "adasparse_bwd: null pointer");
-    const int B = d->B, E = d->E, chunks = (int)L.chunks;
+    const int B = d->B, E = d->E, chunks = (int)L.rows.chunks;
     float* gbuf[2] = {workspace + L.w_g, workspace + L.w_g + (size_t)B * L.max_w};
     float* dd = workspace + L.w_dd;
     float* part = workspace + L.w_part;
     int cur = 0;
     const float* gin = dlogit;      // the DNN alone: dlogit is dh_L [B, n_L], put under h_L's relu mask by the first ada_dd_kernel
     if (d->final_w) {   // the logit layer: d final_w = dlogit^T h_L, d out_bias = sum dlogit, g_L = dlogit final_w under the relu mask of h_L
-        const int K = L.N[L.nl - 1];
-        const float* hL = saved + L.s_h[L.nl - 1];
-        const int ktiles = (int)ceil_div(K, kTN);
-        float *part_w = part, *part_b = part + (size_t)chunks * K;
-        mmoe_dw_kernel<false><<<(unsigned)(chunks * ktiles), kThreads, 0, st>>>(dlogit, 1, 1, hL, K, 0, nullptr, nullptr, B, K, 1, 0, 1, 1,
-                                                                               ktiles, part_w, part_b);
-        SATRANS_CHECK_LAUNCH("mmoe_dw_kernel (adasparse logit layer)");
-        mmoe_reduce_kernel<false><<<(unsigned)ceil_div(K + 1, kThreads), kThreads, 0, st>>>(part_w, part_b, nullptr, B, K, 1, 0, 1, 1, chunks,
-                                                                                           g->final_w, g->out_bias);
-        SATRANS_CHECK_LAUNCH("mmoe_reduce_kernel (adasparse logit layer)");
-        mmoe_gemm_kernel<true, false><<<(unsigned)(L.tiles * ktiles), kThreads, 0, st>>>(dlogit, 1, 0, nullptr, nullptr, B, 1, K, 0, 1, ktiles,
-                                                                                        d->final_w, nullptr, 0, hL, 0, gbuf[cur], K, 0);
-        SATRANS_CHECK_LAUNCH("mmoe_gemm_kernel (adasparse logit layer backward)");
+        const Lyr fin{L.N[L.nl - 1], 1, 1, d->final_w, d->out_bias, g->final_w, g->out_bias};
+        if ((rc = launch_bwd<false>(L.rows, fin, dlogit, 1, saved + L.s_h[L.nl - 1], fin.K, 0, true, 0, gbuf[cur], part, st))) return rc;
         gin = gbuf[cur];
     }
     for (int l = L.nl - 1; l >= 0; --l) {
@@ -488,7 +468,7 @@ extern "C" int satrans_adasparse_bwd(const satrans_adasparse_desc* d, const floa
                                                                                              chunks, g->prn_w[l], g->prn_b[l]);
         SATRANS_CHECK_LAUNCH("mmoe_reduce_kernel (adasparse pruners)");
         float* din = l > 0 ? gbuf[cur ^ 1] : dx;
-        ada_din_kernel<<<(unsigned)(L.tiles * ktiles), kThreads, 0, st>>>(dd, B, K, E, N, ktiles, d->lin_w[l], d->prn_w[l],
+        ada_din_kernel<<<(unsigned)(L.rows.tiles * ktiles), kThreads, 0, st>>>(dd, B, K, E, N, ktiles, d->lin_w[l], d->prn_w[l],
                                                                          l > 0 ? hin : nullptr, l < L.nl - 1, din, demb);
         SATRANS_CHECK_LAUNCH("ada_din_kernel");
         cur ^= 1;

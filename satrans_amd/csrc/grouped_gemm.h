@@ -2,7 +2,8 @@
 // towers (star.hip), its weight-gradient and reduce kernels, and the softmax mixture over up to 8 experts.  Every kernel sits
 // in an unnamed namespace: each file that includes this header gets its own copies, under the names mmoe.hip gave them.
 // star.hip wraps the same tile body with the shared factor switched on (SHARED: W_dom * W_sh on operand load, b_dom + b_sh)
-// and the weight-gradient body with G = 1 as a constant.
+// and the weight-gradient body with G = 1 as a constant.  This header is device code only; the host code that launches it for
+// the four heads (a layer, a batch, launch_fwd / launch_bwd, the grid check, the walks over a DNN) is head_layers.h.
 //
 // Layout.  Rows, hidden rows, dz and dx stay in the caller's row order.  The hidden rows of G blocks of a layer sit side by
 // side: [B, G * n_l], block g in columns [g n_l, (g + 1) n_l).  A workgroup owns (one row tile of kTM rows) x (one tile of kTN

@@ -3,8 +3,9 @@
 // experts run over all rows (dense products) and a row goes through its OWN task's gate, mixture, tower and logit only
 // (scenario-grouped products over order / seg, walked as seg_walk.h describes).
 //
-// Layout, the tile product and the kernels themselves are in grouped_gemm.h, shared with ple.hip; this file holds the layout
-// of the saved rows and the workspace, the validation and the launches.
+// Layout, the tile product and the kernels themselves are in grouped_gemm.h; the launches of a layer, the walks over a DNN and
+// over the expert stack and the per-layer grid check are in head_layers.h, shared with the other heads.  This file holds the
+// layout of the saved rows and the workspace, the validation and the order of the launches.
 //
 //   forward   mmoe_gemm_kernel<false, false>   experts: layer 1 is one product with N = E n_1 over x, layer l >= 2 has E groups
 //             mmoe_gemm_kernel<false, true>    gate DNN and gate_dnn_final_layer of the row's task -> scores [B,E]
@@ -19,30 +20,19 @@
 //             sums of the fp32 partials; a task without rows gets zeros), then mmoe_gemm_kernel<true, .> for the input gradient.
 // No floating-point atomics anywhere: equal inputs give equal bits, and a task's rows give the same bits alone as in a mix
 // (logits, dx rows, that task's gate / tower / out-bias gradients; the experts' gradients sum over all rows).
-#include <algorithm>
-
-#include "grouped_gemm.h"
+#include "head_layers.h"
 
 namespace satrans {
 namespace {
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 
-// a layer of one of the three DNNs as the launches see it: G groups of [N, K] weights (G = 1 for routed layers and for the
-// experts' first layer, whose E blocks share x and so form one product of N = E n_1)
-struct Lyr {
-    int K, N, G;
-    const float *w, *b;
-    float *gw, *gb;
-};
-
 struct MmoeLayout {
-    int nx, ng, nt;                                   // layers of the three chains (gate and tower: hidden + final)
-    Lyr x[kMaxH], g[kMaxH + 1], t[kMaxH + 1];
-    int64_t slots, dw_slots, tiles, chunks;
+    Chain x, g, t;      // experts (dense), gate and tower (routed; hidden + final)
+    Rows rows;
     int64_t n_last;                                   // width of an expert's output
     // saved (floats from its start): gates [B,E], mixture [B,n_last], scores [B,E], then the hidden rows
-    int64_t s_gates, s_mix, s_scores, s_x[kMaxH], s_g[kMaxH], s_t[kMaxH], saved;
+    int64_t s_gates, s_mix, s_scores, saved;
     // workspace: two dz buffers [B, max_w], dscores [B,E], the partials of the layer in hand
     int64_t max_w, w_dz, w_dscores, w_part, total;
 };
@@ -63,70 +53,32 @@ int mmoe_validate(const satrans_mmoe_desc* d, const char* who, MmoeLayout& L) {
         SATRANS_REQUIRE(d->tower_width[l] > 0, SATRANS_E_BADARG, "%s: bad sizes tower_width[%d]=%d", who, l, d->tower_width[l]);
     SATRANS_REQUIRE(d->T <= 65535, SATRANS_E_UNSUPPORTED, "%s: T=%d tasks (65535 at most)", who, d->T);
     const int64_t B = d->B, E = d->E;
-    L.nx = d->n_expert, L.ng = d->n_gate + 1, L.nt = d->n_tower + 1;
-    int prev = d->C;
-    for (int l = 0; l < L.nx; ++l) {
-        const int n = d->expert_width[l];
-        SATRANS_REQUIRE(E * n <= 0x7fffffffLL / 4, SATRANS_E_UNSUPPORTED, "%s: E * expert_width[%d] = %lld", who, l, (long long)(E * n));
-        L.x[l] = l == 0 ? Lyr{prev, (int)(E * n), 1, d->expert_w[l], d->expert_b[l], nullptr, nullptr}
-                        : Lyr{prev, n, (int)E, d->expert_w[l], d->expert_b[l], nullptr, nullptr};
-        prev = n;
-    }
-    L.n_last = prev;
-    prev = d->C;
-    for (int l = 0; l < L.ng; ++l) {
-        const bool fin = l == L.ng - 1;
-        L.g[l] = Lyr{prev, fin ? (int)E : d->gate_width[l], 1, fin ? d->gate_final_w : d->gate_w[l], fin ? nullptr : d->gate_b[l],
-                     nullptr, nullptr};
-        prev = L.g[l].N;
-    }
-    prev = (int)L.n_last;
-    for (int l = 0; l < L.nt; ++l) {
-        const bool fin = l == L.nt - 1;
-        L.t[l] = Lyr{prev, fin ? 1 : d->tower_width[l], 1, fin ? d->tower_final_w : d->tower_w[l], fin ? d->out_bias : d->tower_b[l],
-                     nullptr, nullptr};
-        prev = L.t[l].N;
-    }
-    L.slots = seg_slots(B, d->T, kTM);
-    L.dw_slots = seg_slots(B, d->T, kDwChunk);
-    L.tiles = ceil_div(B, kTM);
-    L.chunks = ceil_div(B, kDwChunk);
+    for (int l = 0; l < d->n_expert; ++l)
+        SATRANS_REQUIRE(E * d->expert_width[l] <= 0x7fffffffLL / 4, SATRANS_E_UNSUPPORTED, "%s: E * expert_width[%d] = %lld", who, l,
+                        (long long)(E * d->expert_width[l]));
+    L.n_last = d->expert_width[d->n_expert - 1];
+    chain_experts(L.x, false, d->E, d->n_expert, d->expert_width, d->C, d->expert_w, d->expert_b);
+    chain_dnn(L.g, true, d->n_gate, d->gate_width, d->C, d->E, d->gate_w, d->gate_b, d->gate_final_w, nullptr);
+    chain_dnn(L.t, true, d->n_tower, d->tower_width, (int)L.n_last, 1, d->tower_w, d->tower_b, d->tower_final_w, d->out_bias);
+    L.rows = rows_of(d->B, d->T, d->order, d->seg);
     int64_t at = 0, per_part = 0;
-    L.max_w = std::max<int64_t>(L.n_last, E);
+    L.max_w = 0;
     auto take = [&](int64_t n) {
         const int64_t a = at;
         at += B * n;
+        L.max_w = std::max(L.max_w, n);
         return a;
     };
     L.s_gates = take(E);
     L.s_mix = take(L.n_last);
     L.s_scores = take(E);
-    for (int l = 0; l < L.nx; ++l) {
-        const Lyr& y = L.x[l];
-        const int64_t wide = (int64_t)y.N * y.G;
-        L.s_x[l] = take(wide);
-        L.max_w = std::max(L.max_w, wide);
-        per_part = std::max(per_part, L.chunks * y.G * y.N * ((int64_t)y.K + 1));
-        SATRANS_REQUIRE((int64_t)y.N * y.K <= 0x7fffffffLL && L.tiles * y.G * ceil_div(std::max(y.N, y.K), kTN) <= 0x7fffffffLL &&
-                            L.chunks * y.G * ceil_div(y.N, kTM) * ceil_div(y.K, kTN) <= 0x7fffffffLL,
-                        SATRANS_E_UNSUPPORTED, "%s: expert layer %d (%d x %d) at B=%d needs more than 2^31 workgroups", who, l, y.N,
-                        y.K, d->B);
-    }
-    for (int c = 0; c < 2; ++c) {
-        const int nl = c ? L.nt : L.ng;
-        for (int l = 0; l < nl; ++l) {
-            const Lyr& y = c ? L.t[l] : L.g[l];
-            if (l < nl - 1) {
-                (c ? L.s_t : L.s_g)[l] = take(y.N);
-                L.max_w = std::max<int64_t>(L.max_w, y.N);
-            }
-            per_part = std::max(per_part, L.dw_slots * y.N * ((int64_t)y.K + 1));
-            SATRANS_REQUIRE((int64_t)y.N * y.K <= 0x7fffffffLL && L.slots * ceil_div(std::max(y.N, y.K), kTN) <= 0x7fffffffLL &&
-                                L.dw_slots * ceil_div(y.N, kTM) * ceil_div(y.K, kTN) <= 0x7fffffffLL,
-                            SATRANS_E_UNSUPPORTED, "%s: %s layer %d (%d x %d) at B=%d needs more than 2^31 workgroups", who,
-                            c ? "tower" : "gate", l, y.N, y.K, d->B);
-        }
-    }
+    for (int l = 0; l < L.x.n; ++l) L.x.s[l] = take((int64_t)L.x.y[l].N * L.x.y[l].G);
+    int rc;
+    if ((rc = chain_fits(L.rows, L.x, who, "expert", per_part))) return rc;
+    for (int l = 0; l < L.g.n - 1; ++l) L.g.s[l] = take(L.g.y[l].N);
+    if ((rc = chain_fits(L.rows, L.g, who, "gate", per_part))) return rc;
+    for (int l = 0; l < L.t.n - 1; ++l) L.t.s[l] = take(L.t.y[l].N);
+    if ((rc = chain_fits(L.rows, L.t, who, "tower", per_part))) return rc;
     L.saved = at;
     L.w_dz = 0;
     L.w_dscores = 2 * B * L.max_w;
@@ -135,68 +87,12 @@ int mmoe_validate(const satrans_mmoe_desc* d, const char* who, MmoeLayout& L) {
     return SATRANS_OK;
 }
 
-bool mmoe_has_operands(const satrans_mmoe_desc* d) {
-    if (!d->x || !d->order || !d->seg || !d->gate_final_w || !d->tower_final_w || !d->out_bias) return false;
-    for (int l = 0; l < d->n_expert; ++l)
-        if (!d->expert_w[l] || !d->expert_b[l]) return false;
-    for (int l = 0; l < d->n_gate; ++l)
-        if (!d->gate_w[l] || !d->gate_b[l]) return false;
-    for (int l = 0; l < d->n_tower; ++l)
-        if (!d->tower_w[l] || !d->tower_b[l]) return false;
-    return true;
-}
-
-bool mmoe_has_grads(const satrans_mmoe_desc* d, const satrans_mmoe_grads* g) {
-    if (!g || !g->gate_final_w || !g->tower_final_w || !g->out_bias) return false;
-    for (int l = 0; l < d->n_expert; ++l)
-        if (!g->expert_w[l] || !g->expert_b[l]) return false;
-    for (int l = 0; l < d->n_gate; ++l)
-        if (!g->gate_w[l] || !g->gate_b[l]) return false;
-    for (int l = 0; l < d->n_tower; ++l)
-        if (!g->tower_w[l] || !g->tower_b[l]) return false;
-    return true;
-}
-
-// out = epilogue(in W^T) of one layer;  in [B, ldin] with group column offset igo, out [B, G N]
-template <bool ROUTED>
-int launch_fwd(const satrans_mmoe_desc* d, const MmoeLayout& L, const Lyr& y, const float* in, int ldin, int igo, int relu, float* out,
-               hipStream_t st) {
-    const int ntiles = (int)ceil_div(y.N, kTN);
-    const int64_t units = ROUTED ? L.slots : L.tiles * y.G;
-    mmoe_gemm_kernel<false, ROUTED><<<(unsigned)(units * ntiles), kThreads, 0, st>>>(in, ldin, igo, d->order, d->seg, d->B, y.K, y.N, d->T,
-                                                                                     y.G, ntiles, y.w, y.b, relu, nullptr, 0, out,
-                                                                                     y.N * y.G, y.N);
-    SATRANS_CHECK_LAUNCH("mmoe_gemm_kernel (forward)");
-    return SATRANS_OK;
-}
-
-// the backward of one layer: its parameter gradients from (dz, hin), then din = dz W, masked by hin > 0 (when masked), added
-// to what din holds (when add).  dz [B, G N], hin / din [B, ldh] with group column offset hgo.
-template <bool ROUTED>
-int launch_bwd(const satrans_mmoe_desc* d, const MmoeLayout& L, const Lyr& y, const float* dz, const float* hin, int ldh, int hgo,
-               bool masked, int add, float* din, float* workspace, hipStream_t st) {
-    const int64_t NK = (int64_t)y.N * y.K;
-    const int ntiles = (int)ceil_div(y.N, kTM), ktiles = (int)ceil_div(y.K, kTN);
-    const int64_t units = ROUTED ? L.dw_slots : L.chunks * y.G;
-    const int groups = ROUTED ? d->T : y.G;
-    float* part_w = workspace + L.w_part;
-    float* part_b = y.b ? part_w + units * NK : nullptr;
-    mmoe_dw_kernel<ROUTED><<<(unsigned)(units * ntiles * ktiles), kThreads, 0, st>>>(dz, y.N * y.G, y.N, hin, ldh, hgo, d->order, d->seg,
-                                                                                    d->B, y.K, y.N, d->T, y.G, ntiles, ktiles, part_w,
-                                                                                    part_b);
-    SATRANS_CHECK_LAUNCH("mmoe_dw_kernel");
-    const int64_t elems = (NK + (y.b ? y.N : 0)) * groups;
-    mmoe_reduce_kernel<ROUTED><<<(unsigned)ceil_div(elems, kThreads), kThreads, 0, st>>>(part_w, part_b, d->seg, d->B, NK, y.N, d->T,
-                                                                                        groups, 1, (int)L.chunks, y.gw, y.gb);
-    SATRANS_CHECK_LAUNCH("mmoe_reduce_kernel");
-    // contraction over this layer's N outputs, K columns out
-    const int otiles = (int)ceil_div(y.K, kTN);
-    const int64_t gunits = ROUTED ? L.slots : L.tiles * y.G;
-    mmoe_gemm_kernel<true, ROUTED><<<(unsigned)(gunits * otiles), kThreads, 0, st>>>(dz, y.N * y.G, y.N, d->order, d->seg, d->B, y.N, y.K,
-                                                                                    d->T, y.G, otiles, y.w, nullptr, 0,
-                                                                                    masked ? hin : nullptr, add, din, ldh, hgo);
-    SATRANS_CHECK_LAUNCH("mmoe_gemm_kernel (backward)");
-    return SATRANS_OK;
+// every pointer of a satrans_mmoe_desc (P = const float) or a satrans_mmoe_grads (P = float) that the head reads or writes
+template <class P, class S>
+bool mmoe_has(const MmoeLayout& L, const S* g) {
+    return g && g->out_bias && chain_has<P>(L.x, g->expert_w, g->expert_b, nullptr, true) &&
+           chain_has<P>(L.g, g->gate_w, g->gate_b, g->gate_final_w, false) &&
+           chain_has<P>(L.t, g->tower_w, g->tower_b, g->tower_final_w, false);
 }
 
 }  // namespace
@@ -221,38 +117,17 @@ extern "C" int satrans_mmoe_fwd(const satrans_mmoe_desc* d, float* logit, float*
     MmoeLayout L;
     int rc = mmoe_validate(d, "mmoe_fwd", L);
     if (rc) return rc;
-    SATRANS_REQUIRE(mmoe_has_operands(d) && logit && saved, SATRANS_E_BADARG, "mmoe_fwd: null pointer");
+    SATRANS_REQUIRE(d->x && d->order && d->seg && mmoe_has<const float>(L, d) && logit && saved, SATRANS_E_BADARG,
+                    "mmoe_fwd: null pointer");
     const int B = d->B, E = d->E, n_last = (int)L.n_last;
-    // experts: layer 1 over x, then block-diagonal
-    const float* in = d->x;
-    int ldin = d->C;
-    for (int l = 0; l < L.nx; ++l) {
-        float* out = saved + L.s_x[l];
-        if ((rc = launch_fwd<false>(d, L, L.x[l], in, ldin, l == 0 ? 0 : L.x[l].K, 1, out, st))) return rc;
-        in = out;
-        ldin = L.x[l].N * L.x[l].G;
-    }
-    const float* eo = in;
-    // the row's own gate
-    in = d->x;
-    for (int l = 0; l < L.ng; ++l) {
-        const bool fin = l == L.ng - 1;
-        float* out = saved + (fin ? L.s_scores : L.s_g[l]);
-        if ((rc = launch_fwd<true>(d, L, L.g[l], in, L.g[l].K, 0, fin ? 0 : 1, out, st))) return rc;
-        in = out;
-    }
-    mmoe_mix_fwd_kernel<<<(unsigned)ceil_div(B, kMixRows), kThreads, 0, st>>>(saved + L.s_scores, eo, B, E, n_last, saved + L.s_gates,
-                                                                             saved + L.s_mix);
+    // experts over x, then the row's own gate
+    if ((rc = experts_fwd(L.rows, L.x, d->x, d->C, saved, st))) return rc;
+    if ((rc = dnn_fwd<true>(L.rows, L.g, d->x, saved, saved + L.s_scores, st))) return rc;
+    mmoe_mix_fwd_kernel<<<(unsigned)ceil_div(B, kMixRows), kThreads, 0, st>>>(saved + L.s_scores, saved + L.x.s[L.x.n - 1], B, E, n_last,
+                                                                             saved + L.s_gates, saved + L.s_mix);
     SATRANS_CHECK_LAUNCH("mmoe_mix_fwd_kernel");
     // the row's own tower, final layer and out bias
-    in = saved + L.s_mix;
-    for (int l = 0; l < L.nt; ++l) {
-        const bool fin = l == L.nt - 1;
-        float* out = fin ? logit : saved + L.s_t[l];
-        if ((rc = launch_fwd<true>(d, L, L.t[l], in, L.t[l].K, 0, fin ? 0 : 1, out, st))) return rc;
-        in = out;
-    }
-    return SATRANS_OK;
+    return dnn_fwd<true>(L.rows, L.t, saved + L.s_mix, saved, logit, st);
 }
 
 extern "C" int satrans_mmoe_bwd(const satrans_mmoe_desc* d, const float* dlogit, float* dx, const float* saved, float* workspace,
@@ -261,59 +136,27 @@ extern "C" int satrans_mmoe_bwd(const satrans_mmoe_desc* d, const float* dlogit,
     MmoeLayout L;
     int rc = mmoe_validate(d, "mmoe_bwd", L);
     if (rc) return rc;
-    SATRANS_REQUIRE(mmoe_has_operands(d) && dlogit && dx && saved && workspace && mmoe_has_grads(d, g), SATRANS_E_BADARG,
-                    "mmoe_bwd: null pointer");
-    for (int l = 0; l < L.nx; ++l) L.x[l].gw = g->expert_w[l], L.x[l].gb = g->expert_b[l];
-    for (int l = 0; l < L.ng; ++l) {
-        const bool fin = l == L.ng - 1;
-        L.g[l].gw = fin ? g->gate_final_w : g->gate_w[l];
-        L.g[l].gb = fin ? nullptr : g->gate_b[l];
-    }
-    for (int l = 0; l < L.nt; ++l) {
-        const bool fin = l == L.nt - 1;
-        L.t[l].gw = fin ? g->tower_final_w : g->tower_w[l];
-        L.t[l].gb = fin ? g->out_bias : g->tower_b[l];
-    }
+    SATRANS_REQUIRE(d->x && d->order && d->seg && mmoe_has<const float>(L, d) && dlogit && dx && saved && workspace &&
+                        mmoe_has<float>(L, g),
+                    SATRANS_E_BADARG, "mmoe_bwd: null pointer");
+    set_grads(L.x, g->expert_w, g->expert_b, nullptr, nullptr, true);
+    set_grads(L.g, g->gate_w, g->gate_b, g->gate_final_w, nullptr, false);
+    set_grads(L.t, g->tower_w, g->tower_b, g->tower_final_w, g->out_bias, false);
     const int B = d->B, E = d->E, n_last = (int)L.n_last;
     float* buf[2] = {workspace + L.w_dz, workspace + L.w_dz + (size_t)B * L.max_w};
     float* dscores = workspace + L.w_dscores;
+    float* part = workspace + L.w_part;
     int cur = 0;      // the buffer the next product writes
-    // tower: dlogit -> dm
-    const float* dz = dlogit;
-    for (int l = L.nt - 1; l >= 0; --l) {
-        const float* hin = saved + (l == 0 ? L.s_mix : L.s_t[l - 1]);
-        if ((rc = launch_bwd<true>(d, L, L.t[l], dz, hin, L.t[l].K, 0, l > 0, 0, buf[cur], workspace, st))) return rc;
-        dz = buf[cur];
-        cur ^= 1;
-    }
+    // tower: dlogit -> dm, in the buffer before `cur`
+    if ((rc = dnn_bwd<true>(L.rows, L.t, dlogit, saved + L.s_mix, saved, 0, nullptr, buf, cur, part, st))) return rc;
     // mixture and softmax: dm -> dz of the experts' last layer, dscores
-    const float* eo = saved + L.s_x[L.nx - 1];
-    mmoe_mix_bwd_kernel<<<(unsigned)ceil_div(B, kMixRows), kThreads, 0, st>>>(dz, saved + L.s_gates, eo, B, E, n_last, buf[cur], dscores);
+    const float* eo = saved + L.x.s[L.x.n - 1];
+    mmoe_mix_bwd_kernel<<<(unsigned)ceil_div(B, kMixRows), kThreads, 0, st>>>(buf[cur ^ 1], saved + L.s_gates, eo, B, E, n_last, buf[cur],
+                                                                             dscores);
     SATRANS_CHECK_LAUNCH("mmoe_mix_bwd_kernel");
-    dz = buf[cur];
+    const float* dz = buf[cur];
     cur ^= 1;
-    // experts (dense): the last product writes dx
-    for (int l = L.nx - 1; l >= 0; --l) {
-        const Lyr& y = L.x[l];
-        if (l == 0) {
-            if ((rc = launch_bwd<false>(d, L, y, dz, d->x, d->C, 0, false, 0, dx, workspace, st))) return rc;
-        } else {
-            if ((rc = launch_bwd<false>(d, L, y, dz, saved + L.s_x[l - 1], y.K * y.G, y.K, true, 0, buf[cur], workspace, st))) return rc;
-            dz = buf[cur];
-            cur ^= 1;
-        }
-    }
-    // gate (routed): the last product adds its dx to the experts'
-    dz = dscores;
-    for (int l = L.ng - 1; l >= 0; --l) {
-        const Lyr& y = L.g[l];
-        if (l == 0) {
-            if ((rc = launch_bwd<true>(d, L, y, dz, d->x, d->C, 0, false, 1, dx, workspace, st))) return rc;
-        } else {
-            if ((rc = launch_bwd<true>(d, L, y, dz, saved + L.s_g[l - 1], y.K, 0, true, 0, buf[cur], workspace, st))) return rc;
-            dz = buf[cur];
-            cur ^= 1;
-        }
-    }
-    return SATRANS_OK;
+    // experts (dense): the last product WRITES dx;  gate (routed): the last product ADDS its dx to the experts'
+    if ((rc = experts_bwd(L.rows, L.x, dz, d->x, d->C, saved, dx, buf, cur, part, st))) return rc;
+    return dnn_bwd<true>(L.rows, L.g, dscores, d->x, saved, 1, dx, buf, cur, part, st);
 }

@@ -5,9 +5,9 @@
 // t's last-level experts, gate and tower - routed; the last level's shared experts over the shared mixture - dense; the last
 // level's shared gate - not at all.  That is what runs here (include/satrans_hip.h states the arithmetic).
 //
-// Every product, weight gradient and reduce is grouped_gemm.h's; the last level's mixture and its backward are
-// mmoe_mix_fwd_kernel / mmoe_mix_bwd_kernel with E = ns + nsh over [B, (ns + nsh) n]: the task's routed specific experts,
-// then the dense shared ones.  New here: the level-0 CGC mixture, a wave per row.
+// Every product, weight gradient and reduce is grouped_gemm.h's, launched and walked by head_layers.h; the last level's mixture
+// and its backward are mmoe_mix_fwd_kernel / mmoe_mix_bwd_kernel with E = ns + nsh over [B, (ns + nsh) n]: the task's routed
+// specific experts, then the dense shared ones.  New here: the level-0 CGC mixture, a wave per row.
 //
 //   forward   level 0 (two levels only): experts dense (layer 1 one product with N = E0 n_1, then E0 groups), own gate
 //             routed, shared gate dense, ple_cgc_fwd_kernel -> both softmaxes, own and shared mixture;
@@ -20,9 +20,7 @@
 // No floating-point atomics anywhere, no scratch: equal inputs give equal bits, and a task's rows give the same bits alone as
 // in a mix (logits, dx rows, the task's gates on both levels, last-level experts, tower, out bias); the dense gradients sum
 // over all rows in the caller's order.
-#include <algorithm>
-
-#include "grouped_gemm.h"
+#include "head_layers.h"
 
 namespace satrans {
 namespace {
@@ -173,28 +171,11 @@ __global__ __launch_bounds__(kThreads) void ple_cgc_bwd_kernel(const int32_t* __
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 
-// a layer as the launches see it: G blocks of [N, K] weights per group of parameters (dense: G blocks in all; routed: G blocks
-// of every task).  G = 1 for gates, towers and for a first expert layer, whose blocks share their input and so form one
-// product of N = blocks * n_1.
-struct Lyr {
-    int K, N, G;
-    const float *w, *b;
-    float *gw, *gb;
-};
-
-// a DNN (and, for gates and towers, its final layer) and where its hidden rows are saved
-struct Chain {
-    int n;
-    bool routed;
-    Lyr y[kMaxH + 1];
-    int64_t s[kMaxH + 1];
-};
-
 struct PleLayout {
     int two;                                          // levels == 2
     int Eo, E0, n_last, kin;                          // own and all blocks, an expert's output width, the last level's input width
     Chain e0, g0, sg0, spec, shr, gate, tower;
-    int64_t slots, dw_slots, tiles, chunks;
+    Rows rows;
     // saved: the last level first (gates, mixture, scores as the MMoE head saves them), then level 0
     int64_t s_gates, s_mix, s_scores, s_g_own, s_g_sh, s_m_own, s_m_sh, s_sc_own, s_sc_sh, saved;
     // workspace: two dz buffers [B, max_w], d mixture, the three dscores, d own mixture, d shared mixture, the partials of the layer in hand
@@ -231,38 +212,14 @@ int ple_validate(const satrans_ple_desc* d, const char* who, PleLayout& L) {
     for (int l = 0; l < nx; ++l)
         SATRANS_REQUIRE((int64_t)std::max(L.two ? L.E0 : 0, L.Eo) * d->expert_width[l] <= 0x7fffffffLL / 4, SATRANS_E_UNSUPPORTED,
                         "%s: blocks * expert_width[%d] = %lld", who, l, (long long)std::max(L.two ? L.E0 : 0, L.Eo) * d->expert_width[l]);
-    // an expert DNN of `blocks` blocks over `in` columns
-    auto experts = [&](Chain& c, bool routed, int blocks, int in, const float* const* w, const float* const* b) {
-        c.n = nx, c.routed = routed;
-        int prev = in;
-        for (int l = 0; l < nx; ++l) {
-            const int n = d->expert_width[l];
-            c.y[l] = l == 0 ? Lyr{prev, blocks * n, 1, w[l], b[l], nullptr, nullptr} : Lyr{prev, n, blocks, w[l], b[l], nullptr, nullptr};
-            prev = n;
-        }
-    };
-    // a gate or tower DNN over `in` columns and its final layer of `fin` outputs
-    auto dnn = [&](Chain& c, bool routed, int hidden, const int32_t* width, int in, int fin, const float* const* w,
-                   const float* const* b, const float* final_w, const float* final_b) {
-        c.n = hidden + 1, c.routed = routed;
-        int prev = in;
-        for (int l = 0; l < c.n; ++l) {
-            const bool last = l == c.n - 1;
-            c.y[l] = Lyr{prev, last ? fin : width[l], 1, last ? final_w : w[l], last ? final_b : b[l], nullptr, nullptr};
-            prev = c.y[l].N;
-        }
-    };
-    experts(L.e0, false, L.E0, d->C, d->e0_w, d->e0_b);
-    dnn(L.g0, true, d->n_gate, d->gate_width, d->C, L.Eo, d->g0_w, d->g0_b, d->g0_final_w, nullptr);
-    dnn(L.sg0, false, d->n_gate, d->gate_width, d->C, L.E0, d->sg0_w, d->sg0_b, d->sg0_final_w, nullptr);
-    experts(L.spec, true, d->ns, L.kin, d->spec_w, d->spec_b);
-    experts(L.shr, false, d->nsh, L.kin, d->shared_w, d->shared_b);
-    dnn(L.gate, true, d->n_gate, d->gate_width, L.kin, L.Eo, d->gate_w, d->gate_b, d->gate_final_w, nullptr);
-    dnn(L.tower, true, d->n_tower, d->tower_width, L.n_last, 1, d->tower_w, d->tower_b, d->tower_final_w, d->out_bias);
-    L.slots = seg_slots(B, d->T, kTM);
-    L.dw_slots = seg_slots(B, d->T, kDwChunk);
-    L.tiles = ceil_div(B, kTM);
-    L.chunks = ceil_div(B, kDwChunk);
+    chain_experts(L.e0, false, L.E0, nx, d->expert_width, d->C, d->e0_w, d->e0_b);
+    chain_dnn(L.g0, true, d->n_gate, d->gate_width, d->C, L.Eo, d->g0_w, d->g0_b, d->g0_final_w, nullptr);
+    chain_dnn(L.sg0, false, d->n_gate, d->gate_width, d->C, L.E0, d->sg0_w, d->sg0_b, d->sg0_final_w, nullptr);
+    chain_experts(L.spec, true, d->ns, nx, d->expert_width, L.kin, d->spec_w, d->spec_b);
+    chain_experts(L.shr, false, d->nsh, nx, d->expert_width, L.kin, d->shared_w, d->shared_b);
+    chain_dnn(L.gate, true, d->n_gate, d->gate_width, L.kin, L.Eo, d->gate_w, d->gate_b, d->gate_final_w, nullptr);
+    chain_dnn(L.tower, true, d->n_tower, d->tower_width, L.n_last, 1, d->tower_w, d->tower_b, d->tower_final_w, d->out_bias);
+    L.rows = rows_of(d->B, d->T, d->order, d->seg);
     int64_t at = 0, per_part = 0;
     L.max_w = std::max<int64_t>(L.n_last, L.two ? L.E0 : L.Eo);
     auto take = [&](int64_t n) {
@@ -271,20 +228,7 @@ int ple_validate(const satrans_ple_desc* d, const char* who, PleLayout& L) {
         L.max_w = std::max(L.max_w, n);
         return a;
     };
-    // the grids and the partials of a chain's layers
-    auto fits = [&](const Chain& c, const char* name) -> int {
-        for (int l = 0; l < c.n; ++l) {
-            const Lyr& y = c.y[l];
-            const int64_t rows = (c.routed ? L.slots : L.tiles) * y.G, units = (c.routed ? L.dw_slots : L.chunks) * y.G;
-            per_part = std::max(per_part, units * y.N * ((int64_t)y.K + 1));
-            SATRANS_REQUIRE((int64_t)y.N * y.K <= 0x7fffffffLL && rows * ceil_div(std::max(y.N, y.K), kTN) <= 0x7fffffffLL &&
-                                units * ceil_div(y.N, kTM) * ceil_div(y.K, kTN) <= 0x7fffffffLL &&
-                                ((int64_t)y.N * y.K + y.N) * y.G * (c.routed ? d->T : 1) <= 0x7fffffffLL * (int64_t)kThreads,
-                            SATRANS_E_UNSUPPORTED, "%s: %s layer %d (%d x %d) at B=%d needs more than 2^31 workgroups", who, name, l, y.N,
-                            y.K, d->B);
-        }
-        return SATRANS_OK;
-    };
+    auto fits = [&](const Chain& c, const char* name) { return chain_fits(L.rows, c, who, name, per_part); };
     int rc;
     L.s_gates = take(L.Eo);
     L.s_mix = take(L.n_last);
@@ -326,14 +270,6 @@ int ple_validate(const satrans_ple_desc* d, const char* who, PleLayout& L) {
     return SATRANS_OK;
 }
 
-template <class P>
-bool chain_has(const Chain& c, P* const* w, P* const* b, P* final_w, bool experts) {
-    const int hidden = experts ? c.n : c.n - 1;
-    for (int l = 0; l < hidden; ++l)
-        if (!w[l] || !b[l]) return false;
-    return experts || final_w;
-}
-
 // every pointer of a satrans_ple_desc (P = const float) or a satrans_ple_grads (P = float) that the head reads or writes
 template <class P, class S>
 bool ple_has(const PleLayout& L, const S* g) {
@@ -344,80 +280,6 @@ bool ple_has(const PleLayout& L, const S* g) {
     return chain_has<P>(L.spec, g->spec_w, g->spec_b, nullptr, true) && chain_has<P>(L.shr, g->shared_w, g->shared_b, nullptr, true) &&
            chain_has<P>(L.gate, g->gate_w, g->gate_b, g->gate_final_w, false) &&
            chain_has<P>(L.tower, g->tower_w, g->tower_b, g->tower_final_w, false);
-}
-
-void set_grads(Chain& c, float* const* w, float* const* b, float* final_w, float* final_b, bool experts) {
-    for (int l = 0; l < c.n; ++l) {
-        const bool fin = !experts && l == c.n - 1;
-        c.y[l].gw = fin ? final_w : w[l];
-        c.y[l].gb = fin ? final_b : b[l];
-    }
-}
-
-// out[:, block * ogo + n] = epilogue(in[:, block * igo + k] W^T) of one layer; in / out are rows of ldin / ldout floats
-template <bool ROUTED>
-int launch_fwd(const satrans_ple_desc* d, const PleLayout& L, const Lyr& y, const float* in, int ldin, int igo, int relu, float* out,
-               int ldout, int ogo, hipStream_t st) {
-    const int ntiles = (int)ceil_div(y.N, kTN);
-    const int64_t units = (ROUTED ? L.slots : L.tiles) * y.G;
-    mmoe_gemm_kernel<false, ROUTED><<<(unsigned)(units * ntiles), kThreads, 0, st>>>(in, ldin, igo, d->order, d->seg, d->B, y.K, y.N, d->T,
-                                                                                     y.G, ntiles, y.w, y.b, relu, nullptr, 0, out, ldout,
-                                                                                     ogo);
-    SATRANS_CHECK_LAUNCH("mmoe_gemm_kernel (ple forward)");
-    return SATRANS_OK;
-}
-
-// the backward of one layer: its parameter gradients from (dz, hin), then din = dz W, masked by hin > 0 (when masked), added
-// to what din holds (when add).  dz rows of ldz floats with block offset y.N; hin / din rows of ldh floats with block offset hgo.
-template <bool ROUTED>
-int launch_bwd(const satrans_ple_desc* d, const PleLayout& L, const Lyr& y, const float* dz, int ldz, const float* hin, int ldh,
-               int hgo, bool masked, int add, float* din, float* workspace, hipStream_t st) {
-    const int64_t NK = (int64_t)y.N * y.K;
-    const int ntiles = (int)ceil_div(y.N, kTM), ktiles = (int)ceil_div(y.K, kTN);
-    const int64_t units = (ROUTED ? L.dw_slots : L.chunks) * y.G;
-    const int groups = (ROUTED ? d->T : 1) * y.G;
-    float* part_w = workspace + L.w_part;
-    float* part_b = y.b ? part_w + units * NK : nullptr;
-    mmoe_dw_kernel<ROUTED><<<(unsigned)(units * ntiles * ktiles), kThreads, 0, st>>>(dz, ldz, y.N, hin, ldh, hgo, d->order, d->seg, d->B,
-                                                                                    y.K, y.N, d->T, y.G, ntiles, ktiles, part_w, part_b);
-    SATRANS_CHECK_LAUNCH("mmoe_dw_kernel (ple)");
-    const int64_t elems = (NK + (y.b ? y.N : 0)) * groups;
-    mmoe_reduce_kernel<ROUTED><<<(unsigned)ceil_div(elems, kThreads), kThreads, 0, st>>>(part_w, part_b, d->seg, d->B, NK, y.N, d->T,
-                                                                                        groups, y.G, (int)L.chunks, y.gw, y.gb);
-    SATRANS_CHECK_LAUNCH("mmoe_reduce_kernel (ple)");
-    const int otiles = (int)ceil_div(y.K, kTN);
-    const int64_t gunits = (ROUTED ? L.slots : L.tiles) * y.G;
-    mmoe_gemm_kernel<true, ROUTED><<<(unsigned)(gunits * otiles), kThreads, 0, st>>>(dz, ldz, y.N, d->order, d->seg, d->B, y.N, y.K, d->T,
-                                                                                    y.G, otiles, y.w, nullptr, 0, masked ? hin : nullptr,
-                                                                                    add, din, ldh, hgo);
-    SATRANS_CHECK_LAUNCH("mmoe_gemm_kernel (ple backward)");
-    return SATRANS_OK;
-}
-
-// a gate or tower DNN and its final layer, forward: hidden rows into saved, the final layer's output into `out`
-template <bool ROUTED>
-int dnn_fwd(const satrans_ple_desc* d, const PleLayout& L, const Chain& c, const float* in, float* saved, float* out, hipStream_t st) {
-    for (int l = 0; l < c.n; ++l) {
-        const bool fin = l == c.n - 1;
-        float* o = fin ? out : saved + c.s[l];
-        if (int rc = launch_fwd<ROUTED>(d, L, c.y[l], in, c.y[l].K, 0, fin ? 0 : 1, o, c.y[l].N, 0, st)) return rc;
-        in = o;
-    }
-    return SATRANS_OK;
-}
-
-// its backward from dz of the final layer; the first layer's input gradient goes to din (written, or added when add)
-template <bool ROUTED>
-int dnn_bwd(const satrans_ple_desc* d, const PleLayout& L, const Chain& c, const float* dz, const float* in, const float* saved,
-            int add, float* din, float* buf[2], int& cur, float* workspace, hipStream_t st) {
-    for (int l = c.n - 1; l >= 0; --l) {
-        const Lyr& y = c.y[l];
-        if (l == 0) return launch_bwd<ROUTED>(d, L, y, dz, y.N, in, y.K, 0, false, add, din, workspace, st);
-        if (int rc = launch_bwd<ROUTED>(d, L, y, dz, y.N, saved + c.s[l - 1], y.K, 0, true, 0, buf[cur], workspace, st)) return rc;
-        dz = buf[cur];
-        cur ^= 1;
-    }
-    return SATRANS_OK;
 }
 
 }  // namespace
@@ -447,21 +309,14 @@ extern "C" int satrans_ple_fwd(const satrans_ple_desc* d, float* logit, float* s
     const int B = d->B, ns = d->ns, n = L.n_last, nx = d->n_expert;
     const float *in_own = d->x, *in_sh = d->x;      // what the last level's specific experts and gate / shared experts read
     if (L.two) {
-        // level 0: every expert over x, layer 1 one product, then block-diagonal
-        const float* in = d->x;
-        int ldin = d->C;
-        for (int l = 0; l < nx; ++l) {
-            const Lyr& y = L.e0.y[l];
-            float* out = saved + L.e0.s[l];
-            if ((rc = launch_fwd<false>(d, L, y, in, ldin, l == 0 ? 0 : y.K, 1, out, y.N * y.G, y.N, st))) return rc;
-            in = out;
-            ldin = y.N * y.G;
-        }
-        if ((rc = dnn_fwd<true>(d, L, L.g0, d->x, saved, saved + L.s_sc_own, st))) return rc;
-        if ((rc = dnn_fwd<false>(d, L, L.sg0, d->x, saved, saved + L.s_sc_sh, st))) return rc;
-        ple_cgc_fwd_kernel<<<(unsigned)ceil_div(B, kMixRows), kThreads, 0, st>>>(d->task, saved + L.s_sc_own, saved + L.s_sc_sh, in, B, d->T,
-                                                                                ns, d->nsh, n, saved + L.s_g_own, saved + L.s_g_sh,
-                                                                                saved + L.s_m_own, saved + L.s_m_sh);
+        // level 0: every expert over x
+        if ((rc = experts_fwd(L.rows, L.e0, d->x, d->C, saved, st))) return rc;
+        if ((rc = dnn_fwd<true>(L.rows, L.g0, d->x, saved, saved + L.s_sc_own, st))) return rc;
+        if ((rc = dnn_fwd<false>(L.rows, L.sg0, d->x, saved, saved + L.s_sc_sh, st))) return rc;
+        ple_cgc_fwd_kernel<<<(unsigned)ceil_div(B, kMixRows), kThreads, 0, st>>>(d->task, saved + L.s_sc_own, saved + L.s_sc_sh,
+                                                                                saved + L.e0.s[nx - 1], B, d->T, ns, d->nsh, n,
+                                                                                saved + L.s_g_own, saved + L.s_g_sh, saved + L.s_m_own,
+                                                                                saved + L.s_m_sh);
         SATRANS_CHECK_LAUNCH("ple_cgc_fwd_kernel");
         in_own = saved + L.s_m_own;
         in_sh = saved + L.s_m_sh;
@@ -473,17 +328,17 @@ extern "C" int satrans_ple_fwd(const satrans_ple_desc* d, float* logit, float* s
         const Lyr &ys = L.spec.y[l], &yh = L.shr.y[l];
         const int w = d->expert_width[l], ld = L.Eo * w;
         float* out = saved + L.spec.s[l];
-        if ((rc = launch_fwd<true>(d, L, ys, hs, ldin, l == 0 ? 0 : ys.K, 1, out, ld, w, st))) return rc;
-        if ((rc = launch_fwd<false>(d, L, yh, hh, ldin, l == 0 ? 0 : yh.K, 1, out + ns * w, ld, w, st))) return rc;
+        if ((rc = launch_fwd<true>(L.rows, ys, hs, ldin, l == 0 ? 0 : ys.K, 1, out, ld, w, st))) return rc;
+        if ((rc = launch_fwd<false>(L.rows, yh, hh, ldin, l == 0 ? 0 : yh.K, 1, out + ns * w, ld, w, st))) return rc;
         hs = out;
         hh = out + ns * w;
         ldin = ld;
     }
-    if ((rc = dnn_fwd<true>(d, L, L.gate, in_own, saved, saved + L.s_scores, st))) return rc;
+    if ((rc = dnn_fwd<true>(L.rows, L.gate, in_own, saved, saved + L.s_scores, st))) return rc;
     mmoe_mix_fwd_kernel<<<(unsigned)ceil_div(B, kMixRows), kThreads, 0, st>>>(saved + L.s_scores, hs, B, L.Eo, n, saved + L.s_gates,
                                                                              saved + L.s_mix);
     SATRANS_CHECK_LAUNCH("mmoe_mix_fwd_kernel (ple)");
-    return dnn_fwd<true>(d, L, L.tower, saved + L.s_mix, saved, logit, st);
+    return dnn_fwd<true>(L.rows, L.tower, saved + L.s_mix, saved, logit, st);
 }
 
 extern "C" int satrans_ple_bwd(const satrans_ple_desc* d, const float* dlogit, float* dx, const float* saved, float* workspace,
@@ -507,6 +362,7 @@ extern "C" int satrans_ple_bwd(const satrans_ple_desc* d, const float* dlogit, f
     const int B = d->B, ns = d->ns, n = L.n_last, nx = d->n_expert;
     float* buf[2] = {workspace, workspace + (size_t)B * L.max_w};
     float* ds1 = workspace + L.w_ds1;
+    float* part = workspace + L.w_part;
     int cur = 0;      // the buffer the next product writes
     // what the last level read, and where the gradient of that goes
     const float* in_own = L.two ? saved + L.s_m_own : d->x;
@@ -515,7 +371,7 @@ extern "C" int satrans_ple_bwd(const satrans_ple_desc* d, const float* dlogit, f
     float* d_sh = L.two ? workspace + L.w_dm_sh : dx;
     // tower: dlogit -> d mixture
     float* dm = workspace + L.w_dm;
-    if ((rc = dnn_bwd<true>(d, L, L.tower, dlogit, saved + L.s_mix, saved, 0, dm, buf, cur, workspace, st))) return rc;
+    if ((rc = dnn_bwd<true>(L.rows, L.tower, dlogit, saved + L.s_mix, saved, 0, dm, buf, cur, part, st))) return rc;
     // mixture and softmax: d mixture -> dz of the experts' last layer, dscores
     mmoe_mix_bwd_kernel<<<(unsigned)ceil_div(B, kMixRows), kThreads, 0, st>>>(dm, saved + L.s_gates, saved + L.spec.s[nx - 1], B, L.Eo, n,
                                                                              buf[cur], ds1);
@@ -527,20 +383,20 @@ extern "C" int satrans_ple_bwd(const satrans_ple_desc* d, const float* dlogit, f
         const Lyr &ys = L.spec.y[l], &yh = L.shr.y[l];
         const int w = d->expert_width[l], ldz = L.Eo * w;
         if (l == 0) {
-            if ((rc = launch_bwd<true>(d, L, ys, dz, ldz, in_own, L.kin, 0, false, 0, d_own, workspace, st))) return rc;
-            if ((rc = launch_bwd<false>(d, L, yh, dz + ns * w, ldz, in_sh, L.kin, 0, false, L.two ? 0 : 1, d_sh, workspace, st))) return rc;
+            if ((rc = launch_bwd<true>(L.rows, ys, dz, ldz, in_own, L.kin, 0, false, 0, d_own, part, st))) return rc;
+            if ((rc = launch_bwd<false>(L.rows, yh, dz + ns * w, ldz, in_sh, L.kin, 0, false, L.two ? 0 : 1, d_sh, part, st))) return rc;
         } else {
             const int wp = d->expert_width[l - 1], ldh = L.Eo * wp;
             const float* hin = saved + L.spec.s[l - 1];
-            if ((rc = launch_bwd<true>(d, L, ys, dz, ldz, hin, ldh, wp, true, 0, buf[cur], workspace, st))) return rc;
-            if ((rc = launch_bwd<false>(d, L, yh, dz + ns * w, ldz, hin + ns * wp, ldh, wp, true, 0, buf[cur] + ns * wp, workspace, st)))
+            if ((rc = launch_bwd<true>(L.rows, ys, dz, ldz, hin, ldh, wp, true, 0, buf[cur], part, st))) return rc;
+            if ((rc = launch_bwd<false>(L.rows, yh, dz + ns * w, ldz, hin + ns * wp, ldh, wp, true, 0, buf[cur] + ns * wp, part, st)))
                 return rc;
             dz = buf[cur];
             cur ^= 1;
         }
     }
     // the last level's gate: its dx is added to the specific experts'
-    if ((rc = dnn_bwd<true>(d, L, L.gate, ds1, in_own, saved, 1, d_own, buf, cur, workspace, st))) return rc;
+    if ((rc = dnn_bwd<true>(L.rows, L.gate, ds1, in_own, saved, 1, d_own, buf, cur, part, st))) return rc;
     if (!L.two) return SATRANS_OK;
     // level 0: both mixtures -> dz of every expert's last layer and both dscores
     float* ds_own = workspace + L.w_ds_own;
@@ -551,17 +407,7 @@ extern "C" int satrans_ple_bwd(const satrans_ple_desc* d, const float* dlogit, f
     SATRANS_CHECK_LAUNCH("ple_cgc_bwd_kernel");
     dz = buf[cur];
     cur ^= 1;
-    for (int l = nx - 1; l >= 0; --l) {
-        const Lyr& y = L.e0.y[l];
-        if (l == 0) {
-            if ((rc = launch_bwd<false>(d, L, y, dz, y.N, d->x, d->C, 0, false, 0, dx, workspace, st))) return rc;
-        } else {
-            if ((rc = launch_bwd<false>(d, L, y, dz, y.N * y.G, saved + L.e0.s[l - 1], y.K * y.G, y.K, true, 0, buf[cur], workspace, st)))
-                return rc;
-            dz = buf[cur];
-            cur ^= 1;
-        }
-    }
-    if ((rc = dnn_bwd<true>(d, L, L.g0, ds_own, d->x, saved, 1, dx, buf, cur, workspace, st))) return rc;
-    return dnn_bwd<false>(d, L, L.sg0, ds_sh, d->x, saved, 1, dx, buf, cur, workspace, st);
+    if ((rc = experts_bwd(L.rows, L.e0, dz, d->x, d->C, saved, dx, buf, cur, part, st))) return rc;
+    if ((rc = dnn_bwd<true>(L.rows, L.g0, ds_own, d->x, saved, 1, dx, buf, cur, part, st))) return rc;
+    return dnn_bwd<false>(L.rows, L.sg0, ds_sh, d->x, saved, 1, dx, buf, cur, part, st);
 }

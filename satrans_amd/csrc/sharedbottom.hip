@@ -3,8 +3,9 @@
 // here the bottom DNN runs over all rows (dense products) and a row goes through its OWN task's tower, final layer and
 // out bias only (scenario-grouped products over order / seg, walked as seg_walk.h describes).
 //
-// Layout, the tile product and the weight-gradient kernels are in grouped_gemm.h, shared with mmoe.hip and ple.hip; this file
-// holds the tower tail, the layout of the saved rows and the workspace, the validation and the launches.
+// Layout, the tile product and the weight-gradient kernels are in grouped_gemm.h; the launches of a layer, the backward walk over
+// a DNN and the per-layer grid check are in head_layers.h, shared with the other heads.  This file holds the tower tail, the
+// layout of the saved rows and the workspace, the validation and the order of the launches.
 //
 //   forward   mmoe_gemm_kernel<false, false>   the bottom DNN, G = 1
 //             mmoe_gemm_kernel<false, true>    the tower's hidden layers except the last, group = task
@@ -22,9 +23,7 @@
 //             mmoe_gemm_kernel<true, .> for the input gradient; the bottom's first layer WRITES dx.
 // No floating-point atomics anywhere: equal inputs give equal bits, and a task's rows give the same bits alone as in a mix
 // (logits, dx rows, that task's tower / final-layer / out-bias gradients; the bottom's gradients sum over all rows).
-#include <algorithm>
-
-#include "grouped_gemm.h"
+#include "head_layers.h"
 
 namespace satrans {
 namespace {
@@ -173,19 +172,11 @@ __global__ __launch_bounds__(kThreads) void sb_tail_bwd_kernel(const float* __re
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 
-// a layer as the launches see it: [N, K] weights (the bottom) or [T, N, K] (the towers)
-struct Lyr {
-    int K, N;
-    const float *w, *b;
-    float *gw, *gb;
-};
-
 struct SbLayout {
-    int nb, nt;      // hidden layers of the bottom and of the towers
-    Lyr b[kMaxH], t[kMaxH];
+    Chain b, t;                // the bottom (dense) and the towers' hidden layers (routed), no final layer: every layer's rows are saved
     int n_bottom, n_tail;      // width of the bottom's last rows; width under the final layer
-    int64_t slots, dw_slots, tiles, chunks;
-    int64_t s_b[kMaxH], s_t[kMaxH], saved;      // saved: the hidden rows, floats from its start
+    Rows rows;
+    int64_t saved;                              // saved: the hidden rows, floats from its start
     int64_t max_w, w_dz, w_part, total;         // workspace: two dz buffers [B, max_w], the partials of the layer in hand
 };
 
@@ -200,36 +191,23 @@ int sb_validate(const satrans_sharedbottom_desc* d, const char* who, SbLayout& L
         SATRANS_REQUIRE(d->tower_width[l] > 0, SATRANS_E_BADARG, "%s: bad sizes tower_width[%d]=%d", who, l, d->tower_width[l]);
     SATRANS_REQUIRE(d->T <= 65535, SATRANS_E_UNSUPPORTED, "%s: T=%d tasks (65535 at most)", who, d->T);
     const int64_t B = d->B;
-    L.nb = d->n_bottom, L.nt = d->n_tower;
-    L.slots = seg_slots(B, d->T, kTM);
-    L.dw_slots = seg_slots(B, d->T, kDwChunk);
-    L.tiles = ceil_div(B, kTM);
-    L.chunks = ceil_div(B, kDwChunk);
+    L.n_bottom = d->bottom_width[d->n_bottom - 1];
+    L.n_tail = d->n_tower ? d->tower_width[d->n_tower - 1] : L.n_bottom;
+    chain_dnn(L.b, false, d->n_bottom, d->bottom_width, d->C, 0, d->bottom_w, d->bottom_b, nullptr, nullptr);
+    chain_dnn(L.t, true, d->n_tower, d->tower_width, L.n_bottom, 0, d->tower_w, d->tower_b, nullptr, nullptr);
+    L.rows = rows_of(d->B, d->T, d->order, d->seg);
     int64_t at = 0, per_part = 0;
     L.max_w = 0;
-    int prev = d->C;
-    for (int c = 0; c < 2; ++c) {
-        const int nl = c ? L.nt : L.nb;
-        const int64_t units = c ? L.slots : L.tiles, dw_units = c ? L.dw_slots : L.chunks;
-        for (int l = 0; l < nl; ++l) {
-            Lyr& y = c ? L.t[l] : L.b[l];
-            y = c ? Lyr{prev, d->tower_width[l], d->tower_w[l], d->tower_b[l], nullptr, nullptr}
-                  : Lyr{prev, d->bottom_width[l], d->bottom_w[l], d->bottom_b[l], nullptr, nullptr};
-            (c ? L.s_t : L.s_b)[l] = at;
-            at += B * y.N;
-            L.max_w = std::max<int64_t>(L.max_w, y.N);
-            per_part = std::max(per_part, dw_units * y.N * ((int64_t)y.K + 1));
-            SATRANS_REQUIRE((int64_t)y.N * y.K <= 0x7fffffffLL && units * ceil_div(std::max(y.N, y.K), kTN) <= 0x7fffffffLL &&
-                                dw_units * ceil_div(y.N, kTM) * ceil_div(y.K, kTN) <= 0x7fffffffLL,
-                            SATRANS_E_UNSUPPORTED, "%s: %s layer %d (%d x %d) at B=%d needs more than 2^31 workgroups", who,
-                            c ? "tower" : "bottom", l, y.N, y.K, d->B);
-            prev = y.N;
+    for (Chain* c : {&L.b, &L.t})
+        for (int l = 0; l < c->n; ++l) {
+            c->s[l] = at;
+            at += B * c->y[l].N;
+            L.max_w = std::max<int64_t>(L.max_w, c->y[l].N);
         }
-        if (!c) L.n_bottom = prev;
-    }
-    L.n_tail = prev;
-    per_part = std::max(per_part, L.dw_slots * ((int64_t)L.n_tail + 1));
-    SATRANS_REQUIRE(L.dw_slots * ceil_div(L.n_tail, 64) <= 0x7fffffffLL, SATRANS_E_UNSUPPORTED,
+    int rc;
+    if ((rc = chain_fits(L.rows, L.b, who, "bottom", per_part)) || (rc = chain_fits(L.rows, L.t, who, "tower", per_part))) return rc;
+    per_part = std::max(per_part, L.rows.dw_slots * ((int64_t)L.n_tail + 1));
+    SATRANS_REQUIRE(L.rows.dw_slots * ceil_div(L.n_tail, 64) <= 0x7fffffffLL, SATRANS_E_UNSUPPORTED,
                     "%s: the final layer (%d wide) at B=%d needs more than 2^31 workgroups", who, L.n_tail, d->B);
     L.saved = at;
     L.w_dz = 0;
@@ -238,60 +216,22 @@ int sb_validate(const satrans_sharedbottom_desc* d, const char* who, SbLayout& L
     return SATRANS_OK;
 }
 
-bool sb_has_operands(const satrans_sharedbottom_desc* d) {
-    if (!d->x || !d->order || !d->seg || !d->tower_final_w || !d->out_bias) return false;
-    for (int l = 0; l < d->n_bottom; ++l)
-        if (!d->bottom_w[l] || !d->bottom_b[l]) return false;
-    for (int l = 0; l < d->n_tower; ++l)
-        if (!d->tower_w[l] || !d->tower_b[l]) return false;
-    return true;
+// every pointer of a satrans_sharedbottom_desc (P = const float) or a satrans_sharedbottom_grads (P = float) that the head
+// reads or writes
+template <class P, class S>
+bool sb_has(const SbLayout& L, const S* g) {
+    return g && g->tower_final_w && g->out_bias && chain_has<P>(L.b, g->bottom_w, g->bottom_b, nullptr, true) &&
+           chain_has<P>(L.t, g->tower_w, g->tower_b, nullptr, true);
 }
 
-bool sb_has_grads(const satrans_sharedbottom_desc* d, const satrans_sharedbottom_grads* g) {
-    if (!g || !g->tower_final_w || !g->out_bias) return false;
-    for (int l = 0; l < d->n_bottom; ++l)
-        if (!g->bottom_w[l] || !g->bottom_b[l]) return false;
-    for (int l = 0; l < d->n_tower; ++l)
-        if (!g->tower_w[l] || !g->tower_b[l]) return false;
-    return true;
-}
-
-// out [B, N] = epilogue(in [B, K] W^T) of one layer
+// the hidden layers [0, n) of a chain, forward: in -> the last of them, every layer's rows into saved
 template <bool ROUTED>
-int launch_fwd(const satrans_sharedbottom_desc* d, const SbLayout& L, const Lyr& y, const float* in, int relu, float* out,
-               hipStream_t st) {
-    const int ntiles = (int)ceil_div(y.N, kTN);
-    const int64_t units = ROUTED ? L.slots : L.tiles;
-    mmoe_gemm_kernel<false, ROUTED><<<(unsigned)(units * ntiles), kThreads, 0, st>>>(in, y.K, 0, d->order, d->seg, d->B, y.K, y.N, d->T, 1,
-                                                                                     ntiles, y.w, y.b, relu, nullptr, 0, out, y.N, y.N);
-    SATRANS_CHECK_LAUNCH("mmoe_gemm_kernel (forward)");
-    return SATRANS_OK;
-}
-
-// the backward of one layer: its parameter gradients from (dz [B,N], hin [B,K]), then din [B,K] = dz W, masked by hin > 0
-// (when masked)
-template <bool ROUTED>
-int launch_bwd(const satrans_sharedbottom_desc* d, const SbLayout& L, const Lyr& y, const float* dz, const float* hin, bool masked,
-               float* din, float* workspace, hipStream_t st) {
-    const int64_t NK = (int64_t)y.N * y.K;
-    const int ntiles = (int)ceil_div(y.N, kTM), ktiles = (int)ceil_div(y.K, kTN);
-    const int64_t units = ROUTED ? L.dw_slots : L.chunks;
-    const int groups = ROUTED ? d->T : 1;
-    float* part_w = workspace + L.w_part;
-    float* part_b = part_w + units * NK;
-    mmoe_dw_kernel<ROUTED><<<(unsigned)(units * ntiles * ktiles), kThreads, 0, st>>>(dz, y.N, y.N, hin, y.K, 0, d->order, d->seg, d->B,
-                                                                                    y.K, y.N, d->T, 1, ntiles, ktiles, part_w, part_b);
-    SATRANS_CHECK_LAUNCH("mmoe_dw_kernel");
-    const int64_t elems = (NK + y.N) * groups;
-    mmoe_reduce_kernel<ROUTED><<<(unsigned)ceil_div(elems, kThreads), kThreads, 0, st>>>(part_w, part_b, d->seg, d->B, NK, y.N, d->T,
-                                                                                        groups, 1, (int)L.chunks, y.gw, y.gb);
-    SATRANS_CHECK_LAUNCH("mmoe_reduce_kernel");
-    const int otiles = (int)ceil_div(y.K, kTN);      // contraction over this layer's N outputs, K columns out
-    const int64_t gunits = ROUTED ? L.slots : L.tiles;
-    mmoe_gemm_kernel<true, ROUTED><<<(unsigned)(gunits * otiles), kThreads, 0, st>>>(dz, y.N, y.N, d->order, d->seg, d->B, y.N, y.K, d->T,
-                                                                                    1, otiles, y.w, nullptr, 0, masked ? hin : nullptr, 0,
-                                                                                    din, y.K, 0);
-    SATRANS_CHECK_LAUNCH("mmoe_gemm_kernel (backward)");
+int hidden_fwd(const Rows& r, const Chain& c, int n, const float*& in, float* saved, hipStream_t st) {
+    for (int l = 0; l < n; ++l) {
+        const Lyr& y = c.y[l];
+        if (int rc = launch_fwd<ROUTED>(r, y, in, y.K, 0, 1, saved + c.s[l], y.N, 0, st)) return rc;
+        in = saved + c.s[l];
+    }
     return SATRANS_OK;
 }
 
@@ -325,33 +265,23 @@ extern "C" int satrans_sharedbottom_fwd(const satrans_sharedbottom_desc* d, floa
     SbLayout L;
     int rc = sb_validate(d, "sharedbottom_fwd", L);
     if (rc) return rc;
-    SATRANS_REQUIRE(sb_has_operands(d) && logit && saved, SATRANS_E_BADARG, "sharedbottom_fwd: null pointer");
+    SATRANS_REQUIRE(d->x && d->order && d->seg && sb_has<const float>(L, d) && logit && saved, SATRANS_E_BADARG,
+                    "sharedbottom_fwd: null pointer");
+    const Rows& R = L.rows;
+    const int nt = L.t.n;
     const float* in = d->x;
-    for (int l = 0; l < L.nb; ++l) {
-        float* out = saved + L.s_b[l];
-        if ((rc = launch_fwd<false>(d, L, L.b[l], in, 1, out, st))) return rc;
-        in = out;
-    }
-    for (int l = 0; l + 1 < L.nt; ++l) {
-        float* out = saved + L.s_t[l];
-        if ((rc = launch_fwd<true>(d, L, L.t[l], in, 1, out, st))) return rc;
-        in = out;
-    }
+    if ((rc = hidden_fwd<false>(R, L.b, L.b.n, in, saved, st))) return rc;
+    if ((rc = hidden_fwd<true>(R, L.t, g_sb_composed ? nt : nt - 1, in, saved, st))) return rc;
     if (g_sb_composed) {
-        if (L.nt > 0) {
-            float* out = saved + L.s_t[L.nt - 1];
-            if ((rc = launch_fwd<true>(d, L, L.t[L.nt - 1], in, 1, out, st))) return rc;
-            in = out;
-        }
-        const Lyr fin{L.n_tail, 1, d->tower_final_w, d->out_bias, nullptr, nullptr};
-        return launch_fwd<true>(d, L, fin, in, 0, logit, st);
+        const Lyr fin{L.n_tail, 1, 1, d->tower_final_w, d->out_bias, nullptr, nullptr};
+        return launch_fwd<true>(R, fin, in, L.n_tail, 0, 0, logit, 1, 0, st);
     }
-    if (L.nt > 0) {
-        const Lyr& y = L.t[L.nt - 1];
-        sb_tail_fwd_kernel<true><<<(unsigned)L.slots, kThreads, 0, st>>>(in, d->order, d->seg, d->B, y.K, y.N, d->T, y.w, y.b,
-                                                                         d->tower_final_w, d->out_bias, saved + L.s_t[L.nt - 1], logit);
+    if (nt > 0) {
+        const Lyr& y = L.t.y[nt - 1];
+        sb_tail_fwd_kernel<true><<<(unsigned)R.slots, kThreads, 0, st>>>(in, d->order, d->seg, d->B, y.K, y.N, d->T, y.w, y.b,
+                                                                         d->tower_final_w, d->out_bias, saved + L.t.s[nt - 1], logit);
     } else {
-        sb_tail_fwd_kernel<false><<<(unsigned)L.slots, kThreads, 0, st>>>(in, d->order, d->seg, d->B, 0, L.n_tail, d->T, nullptr, nullptr,
+        sb_tail_fwd_kernel<false><<<(unsigned)R.slots, kThreads, 0, st>>>(in, d->order, d->seg, d->B, 0, L.n_tail, d->T, nullptr, nullptr,
                                                                           d->tower_final_w, d->out_bias, nullptr, logit);
     }
     SATRANS_CHECK_LAUNCH("sb_tail_fwd_kernel");
@@ -364,42 +294,38 @@ extern "C" int satrans_sharedbottom_bwd(const satrans_sharedbottom_desc* d, cons
     SbLayout L;
     int rc = sb_validate(d, "sharedbottom_bwd", L);
     if (rc) return rc;
-    SATRANS_REQUIRE(sb_has_operands(d) && dlogit && dx && saved && workspace && sb_has_grads(d, g), SATRANS_E_BADARG,
-                    "sharedbottom_bwd: null pointer");
-    for (int l = 0; l < L.nb; ++l) L.b[l].gw = g->bottom_w[l], L.b[l].gb = g->bottom_b[l];
-    for (int l = 0; l < L.nt; ++l) L.t[l].gw = g->tower_w[l], L.t[l].gb = g->tower_b[l];
-    const int B = d->B;
+    SATRANS_REQUIRE(d->x && d->order && d->seg && sb_has<const float>(L, d) && dlogit && dx && saved && workspace && sb_has<float>(L, g),
+                    SATRANS_E_BADARG, "sharedbottom_bwd: null pointer");
+    set_grads(L.b, g->bottom_w, g->bottom_b, nullptr, nullptr, true);
+    set_grads(L.t, g->tower_w, g->tower_b, nullptr, nullptr, true);
+    const Rows& R = L.rows;
+    const int B = d->B, nt = L.t.n;
     float* buf[2] = {workspace + L.w_dz, workspace + L.w_dz + (size_t)B * L.max_w};
+    float* part = workspace + L.w_part;
     int cur = 0;      // the buffer the next product writes
     // the tail: dlogit -> dz of the last tower layer (of the bottom's last layer without one), d tower_final_w, d out_bias
-    const float* h_bottom = saved + L.s_b[L.nb - 1];
+    const float* h_bottom = saved + L.b.s[L.b.n - 1];
     {
-        const float* h = L.nt > 0 ? saved + L.s_t[L.nt - 1] : h_bottom;
+        const float* h = nt > 0 ? saved + L.t.s[nt - 1] : h_bottom;
         const int n = L.n_tail, ntiles = (int)ceil_div(n, 64);
-        float* part_w = workspace + L.w_part;
-        float* part_b = part_w + L.dw_slots * n;
-        sb_tail_bwd_kernel<<<(unsigned)(L.dw_slots * ntiles), kThreads, 0, st>>>(dlogit, h, d->order, d->seg, B, n, d->T, ntiles,
-                                                                                 d->tower_final_w, buf[cur], part_w, part_b);
+        float* part_b = part + R.dw_slots * n;
+        sb_tail_bwd_kernel<<<(unsigned)(R.dw_slots * ntiles), kThreads, 0, st>>>(dlogit, h, d->order, d->seg, B, n, d->T, ntiles,
+                                                                                 d->tower_final_w, buf[cur], part, part_b);
         SATRANS_CHECK_LAUNCH("sb_tail_bwd_kernel");
         mmoe_reduce_kernel<true><<<(unsigned)ceil_div((int64_t)(n + 1) * d->T, kThreads), kThreads, 0, st>>>(
-            part_w, part_b, d->seg, B, n, 1, d->T, d->T, 1, (int)L.chunks, g->tower_final_w, g->out_bias);
+            part, part_b, d->seg, B, n, 1, d->T, d->T, 1, (int)R.chunks, g->tower_final_w, g->out_bias);
         SATRANS_CHECK_LAUNCH("mmoe_reduce_kernel");
     }
     const float* dz = buf[cur];
     cur ^= 1;
     // towers (routed): the first layer's input gradient goes under the bottom's relu mask
-    for (int l = L.nt - 1; l >= 0; --l) {
-        const float* hin = l == 0 ? h_bottom : saved + L.s_t[l - 1];
-        if ((rc = launch_bwd<true>(d, L, L.t[l], dz, hin, true, buf[cur], workspace, st))) return rc;
+    for (int l = nt - 1; l >= 0; --l) {
+        const Lyr& y = L.t.y[l];
+        const float* hin = l == 0 ? h_bottom : saved + L.t.s[l - 1];
+        if ((rc = launch_bwd<true>(R, y, dz, y.N, hin, y.K, 0, true, 0, buf[cur], part, st))) return rc;
         dz = buf[cur];
         cur ^= 1;
     }
     // bottom (dense): the last product writes dx
-    for (int l = L.nb - 1; l >= 0; --l) {
-        if (l == 0) return launch_bwd<false>(d, L, L.b[l], dz, d->x, false, dx, workspace, st);
-        if ((rc = launch_bwd<false>(d, L, L.b[l], dz, saved + L.s_b[l - 1], true, buf[cur], workspace, st))) return rc;
-        dz = buf[cur];
-        cur ^= 1;
-    }
-    return SATRANS_OK;
+    return dnn_bwd<false>(R, L.b, dz, d->x, saved, 0, dx, buf, cur, part, st);
 }
