@@ -40,7 +40,8 @@ extern "C" {
  *    (satrans_star_desc, satrans_star_*), the scenario-routed MMoE head (satrans_mmoe_desc, satrans_mmoe_*) and the
  *    scenario-routed PLE head (satrans_ple_desc, satrans_ple_grads, satrans_ple_*), and AdaSparse's scenario-pruned DNN
  *    (satrans_adasparse_desc, satrans_adasparse_grads, satrans_adasparse_*), and the scenario-routed SharedBottom head
- *    (satrans_sharedbottom_desc, satrans_sharedbottom_grads, satrans_sharedbottom_*). */
+ *    (satrans_sharedbottom_desc, satrans_sharedbottom_grads, satrans_sharedbottom_*), and xDeepFM's compressed interaction
+ *    network (satrans_cin_desc, satrans_cin_grads, satrans_cin_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -689,6 +690,51 @@ int satrans_sharedbottom_fwd(const satrans_sharedbottom_desc* d, float* logit, f
 int satrans_sharedbottom_bwd(const satrans_sharedbottom_desc* d, const float* dlogit, float* dx, const float* saved,
                              float* workspace, const satrans_sharedbottom_grads* g, void* stream);
 int satrans_sharedbottom_set_forward(int composed);
+
+/* Compressed interaction network: deepctr-torch's CIN, the interaction layer of the reference's xDeepFM (models/xdeepfm.py:73,
+ * 96-98).  With X0 = x0 [B, M, D], H_0 = M and X_0 = X0, layer i = 0 .. L-1 of O_i = width[i] channels:
+ *     z_i[b,o,d] = b[i][o] + sum_{h < H_i, m < M} w[i][o, h M + m] X_i[b,h,d] X0[b,m,d]        a_i = relu(z_i)
+ *     split_half and i < L-1:  X_{i+1} = a_i[:, :O_i/2], direct_i = a_i[:, O_i/2:]   (O_i even, else SATRANS_E_BADARG)
+ *     otherwise:               X_{i+1} = direct_i = a_i
+ *     result [B, F] = the direct channels of layer 0, then layer 1, ..., each summed over d (d ascending)
+ * w[i] [O_i, H_i M] (the Conv1d(H_i M, O_i, 1) weight without its last axis), b[i] [O_i].  fp32 throughout, products on the
+ * exact f32-input MFMA.  1 to SATRANS_CIN_MAX_LAYERS layers, 1 to SATRANS_CIN_MAX_FIELDS fields, widths 1 to
+ * SATRANS_CIN_MAX_WIDTH, any positive B and D with B D < 2^31 (SATRANS_E_UNSUPPORTED beyond).
+ * The outer product [B, H_i M, D] of the torch form is never written: a product's rows are the (b, d) pairs r = b D + d, its
+ * contraction index is k = h M + m, and the operand element X_i[b,h,d] X0[b,m,d] is formed from two values in LDS while w[i]
+ * streams.  A workgroup takes SATRANS_CIN_ROW_TILE rows r; a result element is a k-ordered fmaf chain, so a sample's row of
+ * `result` does not depend on the batch around it.
+ * saved: a_i [B, O_i, D] of every layer, layer 0 first - all the backward keeps.  The forward needs no workspace; the
+ * backward's holds dz [B, widest layer, D], dX of the layer above [B, widest hidden part, D] and the per-chunk partials of
+ * the weight gradients of the layer in hand (a chunk = SATRANS_CIN_DW_ROW_CHUNK rows r).  Per layer, last to first:
+ * dz = upstream (a_i > 0); dw[i] = dz^T A and db[i] = sum dz as chunk partials, the operand generated again, merged in chunk
+ * order; dA = dz w[i] is never stored - the workgroup of a row tile walks the tiles of k in order and folds each into
+ * dX_i[b,h,d] += dA X0[b,m,d] and dX0[b,m,d] += dA X_i[b,h,d] (layer 0: both into dX0).  The backward WRITES dx0 [B, M, D]
+ * and every gradient of satrans_cin_grads.  No floating-point atomics: equal inputs give equal bits, and a sample's dx0 rows
+ * are the same bits alone as inside a batch. */
+#define SATRANS_CIN_MAX_LAYERS 4
+#define SATRANS_CIN_MAX_FIELDS 64
+#define SATRANS_CIN_MAX_WIDTH 256
+#define SATRANS_CIN_ROW_TILE 64
+#define SATRANS_CIN_DW_ROW_CHUNK 1024
+typedef struct satrans_cin_desc {
+    int32_t B, M, D, L;
+    int32_t split_half;                     /* 0 or 1 */
+    int32_t reserved;                       /* 0 */
+    int32_t width[SATRANS_CIN_MAX_LAYERS];
+    const float* x0;
+    const float* w[SATRANS_CIN_MAX_LAYERS];
+    const float* b[SATRANS_CIN_MAX_LAYERS];
+} satrans_cin_desc;
+typedef struct satrans_cin_grads {
+    float* w[SATRANS_CIN_MAX_LAYERS];
+    float* b[SATRANS_CIN_MAX_LAYERS];
+} satrans_cin_grads;
+int64_t satrans_cin_saved_floats(const satrans_cin_desc* d);
+int64_t satrans_cin_workspace_floats(const satrans_cin_desc* d);
+int satrans_cin_fwd(const satrans_cin_desc* d, float* result, float* saved, void* stream);
+int satrans_cin_bwd(const satrans_cin_desc* d, const float* dresult, float* dx0, const float* saved, float* workspace,
+                    const satrans_cin_grads* g, void* stream);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

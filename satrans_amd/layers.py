@@ -27,8 +27,12 @@
     pruning factor cut to exactly zero below a threshold, both products of a layer in one launch; and `AdaSparseHead`, the
     part of AdaSparse.forward behind the embeddings (adasparse.py:185-189).  Nothing is routed here (csrc/adasparse.hip).
 
+  * `CIN` - deepctr's compressed interaction network, which the reference's xDeepFM calls (models/xdeepfm.py:73,96-98), with
+    the outer product as a generated operand of the products (csrc/cin.hip); and `XDeepFMHead`, the part of xDeepFM.forward
+    behind the embeddings (xdeepfm.py:94-115).  Single-task: nothing is routed.
+
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
-csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip) wrapped in a
+csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip) wrapped in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -1217,3 +1221,179 @@ class AdaSparseHead(nn.Module):
     def forward(self, dnn_input, domain_emb):
         self.dnn._check(dnn_input, domain_emb, "AdaSparseHead")
         return self.dnn._run(dnn_input, domain_emb, head=(self.dnn_linear.weight, self.out.bias))
+
+
+def _cin_fill(tgt, L, tensors):
+    """Set the w / b pointers of a satrans_cin_desc / satrans_cin_grads from `tensors`: the L weights, then the L biases."""
+    for i in range(L):
+        tgt.w[i], tgt.b[i] = tensors[i].data_ptr(), tensors[L + i].data_ptr()
+    return tgt
+
+
+def _cin_desc(x, split_half, tensors):
+    L = len(tensors) // 2
+    d = _cin_fill(N.CINDesc(), L, tensors)
+    d.B, d.M, d.D, d.L, d.split_half = x.shape[0], x.shape[1], x.shape[2], L, int(split_half)
+    d.x0 = x.data_ptr()
+    for i in range(L):
+        d.width[i] = tensors[i].shape[0]
+    return d
+
+
+class _CINFn(torch.autograd.Function):
+    """result [B, featuremap_num] of the compressed interaction network (csrc/cin.hip); `tensors`: the Conv1d weights
+    [O_i, H_i M, 1] of the layers, then their biases."""
+
+    @staticmethod
+    def forward(ctx, x, split_half, *tensors):
+        lib = N.lib()
+        dev = x.device
+        x = x.contiguous()
+        tensors = tuple(t.contiguous() for t in tensors)
+        d = _cin_desc(x, split_half, tensors)
+        saved = torch.empty(_native_size(lib.satrans_cin_saved_floats, d), dtype=torch.float32, device=dev)
+        L = len(tensors) // 2
+        widths = [t.shape[0] for t in tensors[:L]]
+        F = sum(w - (w // 2 if split_half and i != L - 1 else 0) for i, w in enumerate(widths))
+        result = torch.empty(x.shape[0], F, dtype=torch.float32, device=dev)
+        N.check(lib.satrans_cin_fwd(C.byref(d), result.data_ptr(), saved.data_ptr(), N.stream_handle(dev)), "satrans_cin_fwd")
+        ctx.split_half = split_half
+        ctx.save_for_backward(x, saved, *tensors)
+        ctx.mark_non_differentiable(saved)
+        return result, saved
+
+    @staticmethod
+    def backward(ctx, dresult, _dsaved):
+        lib = N.lib()
+        x, saved, *tensors = ctx.saved_tensors
+        d = _cin_desc(x, ctx.split_half, tensors)
+        work = torch.empty(_native_size(lib.satrans_cin_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        grads = [torch.empty_like(t) for t in tensors]
+        g = _cin_fill(N.CINGrads(), len(tensors) // 2, grads)
+        N.check(lib.satrans_cin_bwd(C.byref(d), dresult.contiguous().data_ptr(), dx.data_ptr(), saved.data_ptr(), work.data_ptr(),
+                                    C.byref(g), N.stream_handle(x.device)), "satrans_cin_bwd")
+        return (dx, None, *grads)
+
+
+class CIN(nn.Module):
+    """deepctr-torch's Compressed Interaction Network, the interaction layer of the reference's xDeepFM (models/xdeepfm.py:73,
+    96-98), with deepctr's constructor: `l2_reg`, `seed` and `device` are accepted and unused.  With X0 = inputs [B, M, D] and
+    X_0 = X0, layer i is `relu(Conv1d(H_i M, O_i, 1)(outer(X_i, X0)))` over the [B, H_i M, D] outer product along the fields;
+    under split_half the first half of a layer's channels feeds the next layer and the second half is output, the last layer is
+    output whole; the output channels of all layers, summed over D, make the result.
+
+    forward(inputs [B, field_size, D] fp32 on the GPU) -> [B, featuremap_num].  The outer product is never materialised: the
+    kernels form its elements from the two factors while the weights stream (csrc/cin.hip), forward and backward, so the memory
+    a call needs is the layers' activations [B, O_i, D].  One autograd.Function runs satrans_cin_fwd / satrans_cin_bwd.
+
+    Parameters are deepctr's, `conv1ds.{i}.weight` [O_i, H_i M, 1] and `conv1ds.{i}.bias` [O_i] with torch's Conv1d default
+    initialisation: the `cin.conv1ds.*` entries of a reference xDeepFM checkpoint load with load_state_dict.
+    Not built - NotImplementedError at construction: an activation other than relu, more than CIN_MAX_LAYERS layers, more
+    than CIN_MAX_FIELDS fields, a layer wider than CIN_MAX_WIDTH.  l2_reg is not applied (main.py leaves l2_reg_cin 0)."""
+
+    def __init__(self, field_size, layer_size=(128, 128), activation='relu', split_half=True, l2_reg=1e-5, seed=1024, device='cpu'):
+        super().__init__()
+        if len(layer_size) == 0:
+            raise ValueError("layer_size must be a list(tuple) of length greater than 1")
+        if activation != 'relu':
+            raise NotImplementedError(f"CIN: activation {activation!r} is not built (relu only)")
+        sizes = [int(s) for s in layer_size]
+        if field_size < 1 or min(sizes) < 1:
+            raise ValueError("CIN: field_size and the layer sizes must be positive")
+        if len(sizes) > N.CIN_MAX_LAYERS:
+            raise NotImplementedError(f"CIN: 1 to {N.CIN_MAX_LAYERS} layers, got {len(sizes)}")
+        if field_size > N.CIN_MAX_FIELDS:
+            raise NotImplementedError(f"CIN: 1 to {N.CIN_MAX_FIELDS} fields, got {field_size}")
+        if max(sizes) > N.CIN_MAX_WIDTH:
+            raise NotImplementedError(f"CIN: layer sizes up to {N.CIN_MAX_WIDTH}, got {max(sizes)}")
+        self.layer_size, self.split_half, self.activation = tuple(sizes), bool(split_half), activation
+        self.field_nums = [int(field_size)]
+        self.conv1ds = nn.ModuleList()
+        for i, size in enumerate(sizes):
+            self.conv1ds.append(nn.Conv1d(self.field_nums[-1] * self.field_nums[0], size, 1))
+            if self.split_half:
+                if i != len(sizes) - 1 and size % 2 > 0:
+                    raise ValueError("layer_size must be even number except for the last layer when split_half=True")
+                self.field_nums.append(size // 2)
+            else:
+                self.field_nums.append(size)
+        self.featuremap_num = sum(sizes[:-1]) // 2 + sizes[-1] if self.split_half else sum(sizes)
+
+    def forward(self, inputs):
+        if inputs.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs.dim()))
+        if inputs.shape[1] != self.field_nums[0]:
+            raise ValueError(f"CIN: expected inputs [B, {self.field_nums[0]}, D], got {tuple(inputs.shape)}")
+        N.require_gpu(inputs, "CIN")
+        if inputs.dtype != torch.float32 or self.conv1ds[0].weight.dtype != torch.float32:
+            raise TypeError("CIN: inputs, parameters and gradients are float32")
+        tensors = [c.weight for c in self.conv1ds] + [c.bias for c in self.conv1ds]
+        result, _ = _CINFn.apply(inputs, self.split_half, *tensors)
+        return result
+
+
+class XDeepFMHead(nn.Module):
+    """The half of the reference's xDeepFM.forward behind the embedding lookup (models/xdeepfm.py:94-115):
+
+        logit = linear_logit + cin_linear(cin(emb)) + dnn_linear(dnn(cat(flatten(emb), dense))) + out.bias
+
+    forward(emb [B, field_size, embedding_size] fp32, dense [B, dense_dim] or None, linear_logit [B,1] or None) -> logit [B,1];
+    the caller applies the sigmoid.  `emb` is the concatenation of the looked-up sparse embeddings in field order; the
+    reference's `metatrans` flag (xdeepfm.py:87-90) transforms that block first, which here is
+
+        head = XDeepFMHead(F, D, dense_dim, ...); meta = MetaTransformation(D, num_domains)
+        logit = head(meta(domain_ids, emb), dense, linear_logit)
+
+    The CIN - 25.8 of xDeepFM's 26.3 MFLOP per sample at the AliCCP shape - is `CIN` above (csrc/cin.hip).  The DNN branch
+    (Linear + relu layers) and the two one-column Linears are plain torch modules: under 2 % of the FLOPs.  Empty
+    dnn_hidden_units or an empty cin_layer_size drops that branch, as the reference does.
+
+    Parameter names, shapes, state_dict order and initialisation are the reference xDeepFM's: out.bias (zeros),
+    dnn.linears.{l}.{weight,bias} (weights N(0, init_std)), dnn_linear.weight, cin.conv1ds.{i}.{weight,bias}, cin_linear.weight
+    - those entries of a reference checkpoint load with load_state_dict.
+    Not built, as in the other heads: l2_reg_*, dropout, batch-norm, activations other than relu."""
+
+    def __init__(self, field_size, embedding_size, dense_dim=0, dnn_hidden_units=(256, 256), cin_layer_size=(256, 128),
+                 cin_split_half=True, init_std=0.0001):
+        super().__init__()
+        if field_size < 1 or embedding_size < 1 or dense_dim < 0:
+            raise ValueError("XDeepFMHead: field_size and embedding_size must be positive, dense_dim non-negative")
+        self.field_size, self.embedding_size, self.dense_dim = int(field_size), int(embedding_size), int(dense_dim)
+        units = [int(u) for u in dnn_hidden_units]
+        self.use_dnn, self.use_cin = len(units) > 0, len(cin_layer_size) > 0
+        # (first: in the reference's state_dict `out.*` precedes xDeepFM's own modules, because its BaseModel registers that name)
+        self.out = _OutBias()
+        if self.use_dnn:
+            self.dnn = _TowerDNN(self.field_size * self.embedding_size + self.dense_dim, units, init_std)
+            self.dnn_linear = nn.Linear(units[-1], 1, bias=False)
+        if self.use_cin:
+            self.cin = CIN(field_size, cin_layer_size, 'relu', cin_split_half)
+            self.featuremap_num = self.cin.featuremap_num
+            self.cin_linear = nn.Linear(self.featuremap_num, 1, bias=False)
+
+    def forward(self, emb, dense=None, linear_logit=None):
+        if emb.dim() != 3 or emb.shape[1] != self.field_size or emb.shape[2] != self.embedding_size:
+            raise ValueError(f"XDeepFMHead: expected emb [B, {self.field_size}, {self.embedding_size}], got {tuple(emb.shape)}")
+        got = 0 if dense is None else (dense.shape[1] if dense.dim() == 2 else -1)
+        if got != self.dense_dim:
+            raise ValueError(f"XDeepFMHead: expected dense [B, {self.dense_dim}], got "
+                             f"{None if dense is None else tuple(dense.shape)}")
+        N.require_gpu(emb, "XDeepFMHead")
+        if emb.dtype != torch.float32:
+            raise TypeError("XDeepFMHead: rows, parameters and gradients are float32")
+        logit = linear_logit      # the reference's order of the sum: linear + dnn + cin, then the bias of `out`
+        if self.use_dnn:
+            h = torch.flatten(emb, start_dim=1)
+            if dense is not None:
+                h = torch.cat([h, dense], dim=-1)
+            for lin in self.dnn.linears:
+                h = torch.relu(lin(h))
+            h = self.dnn_linear(h)
+            logit = h if logit is None else logit + h
+        if self.use_cin:
+            h = self.cin_linear(self.cin(emb))
+            logit = h if logit is None else logit + h
+        if logit is None:
+            return self.out.bias.reshape(1, 1).expand(emb.shape[0], 1)
+        return logit + self.out.bias

@@ -189,6 +189,25 @@ class SharedBottomGrads(C.Structure):
     _fields_ = list(_SHAREDBOTTOM_POINTER_FIELDS)
 
 
+CIN_MAX_LAYERS = 4            # SATRANS_CIN_MAX_LAYERS
+CIN_MAX_FIELDS = 64           # SATRANS_CIN_MAX_FIELDS
+CIN_MAX_WIDTH = 256           # SATRANS_CIN_MAX_WIDTH: channels of one layer
+CIN_ROW_TILE = 64             # SATRANS_CIN_ROW_TILE: (sample, d) rows under a workgroup of the CIN products
+CIN_DW_ROW_CHUNK = 1024       # SATRANS_CIN_DW_ROW_CHUNK: (sample, d) rows that one partial of its weight gradients sums
+
+
+class CINDesc(C.Structure):
+    """Mirror of `satrans_cin_desc`."""
+    _fields_ = [("B", C.c_int32), ("M", C.c_int32), ("D", C.c_int32), ("L", C.c_int32), ("split_half", C.c_int32),
+                ("reserved", C.c_int32), ("width", C.c_int32 * CIN_MAX_LAYERS), ("x0", _vp),
+                ("w", _vp * CIN_MAX_LAYERS), ("b", _vp * CIN_MAX_LAYERS)]
+
+
+class CINGrads(C.Structure):
+    """Mirror of `satrans_cin_grads`."""
+    _fields_ = [("w", _vp * CIN_MAX_LAYERS), ("b", _vp * CIN_MAX_LAYERS)]
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -301,6 +320,10 @@ SIGNATURES = {
     "satrans_sharedbottom_fwd": (C.c_int, [C.POINTER(SharedBottomDesc), _vp, _vp, _vp]),
     "satrans_sharedbottom_bwd": (C.c_int, [C.POINTER(SharedBottomDesc), _vp, _vp, _vp, _vp, C.POINTER(SharedBottomGrads), _vp]),
     "satrans_sharedbottom_set_forward": (C.c_int, [C.c_int]),
+    "satrans_cin_saved_floats": (C.c_int64, [C.POINTER(CINDesc)]),
+    "satrans_cin_workspace_floats": (C.c_int64, [C.POINTER(CINDesc)]),
+    "satrans_cin_fwd": (C.c_int, [C.POINTER(CINDesc), _vp, _vp, _vp]),
+    "satrans_cin_bwd": (C.c_int, [C.POINTER(CINDesc), _vp, _vp, _vp, _vp, C.POINTER(CINGrads), _vp]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
