@@ -41,7 +41,8 @@ extern "C" {
  *    scenario-routed PLE head (satrans_ple_desc, satrans_ple_grads, satrans_ple_*), and AdaSparse's scenario-pruned DNN
  *    (satrans_adasparse_desc, satrans_adasparse_grads, satrans_adasparse_*), and the scenario-routed SharedBottom head
  *    (satrans_sharedbottom_desc, satrans_sharedbottom_grads, satrans_sharedbottom_*), and xDeepFM's compressed interaction
- *    network (satrans_cin_desc, satrans_cin_grads, satrans_cin_*). */
+ *    network (satrans_cin_desc, satrans_cin_grads, satrans_cin_*), and DCN's cross network (satrans_cross_desc,
+ *    satrans_cross_grads, satrans_cross_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -735,6 +736,43 @@ int64_t satrans_cin_workspace_floats(const satrans_cin_desc* d);
 int satrans_cin_fwd(const satrans_cin_desc* d, float* result, float* saved, void* stream);
 int satrans_cin_bwd(const satrans_cin_desc* d, const float* dresult, float* dx0, const float* saved, float* workspace,
                     const satrans_cin_grads* g, void* stream);
+
+/* DCN's cross network: deepctr-torch's CrossNet, which the reference's DCN calls (models/dcn.py:70,101), in its vector
+ * (matrix = 0) and matrix (matrix = 1) forms.  With x0 [B, N], x_0 = x0, l = 0 .. L-1:
+ *     vector:  s_l[b]   = sum_n x_l[b,n] kernels[l][n]          x_{l+1} = x0 s_l[b] + bias[l] + x_l
+ *     matrix:  u_l[b,:] = kernels[l] x_l[b,:] + bias[l]         x_{l+1} = x0 * u_l + x_l       (kernels[l] [n_out, n_in])
+ *     result [B, N] = x_L
+ * kernels [L, N] (deepctr's [L, N, 1]) or [L, N, N], bias [L, N] (deepctr's [L, N, 1]).  fp32 throughout.  1 to
+ * SATRANS_CROSS_MAX_LAYERS layers, 1 to SATRANS_CROSS_MAX_FEATURES features, any positive B whose launches fit 2^31
+ * workgroups (SATRANS_E_UNSUPPORTED beyond); all of that is decided before a device is touched.
+ * Vector form: one launch forward (a wave per row, the row in registers over all layers; x0 read once, result written once)
+ * and one backward launch plus the ordered reduce.  saved = s [B, L]: B L floats.  The backward rebuilds x_l from x0 and s
+ * (x_l = (1 + sum_{j<l} s_j) x0 + sum_{j<l} bias[j]); a workgroup owns SATRANS_CROSS_VEC_ROW_CHUNK rows and leaves one partial
+ * of dkernels and dbias: workspace = 2 ceil(B / SATRANS_CROSS_VEC_ROW_CHUNK) L N floats.
+ * Matrix form: one launch per layer forward, the 64 x 64 f32-MFMA tile product with the cross epilogue.
+ * saved = u_0 .. u_{L-1} [B, N] each, then x_1 .. x_{L-1}: (2 L - 1) B N floats.  workspace = du [B, N], g [B, N] and the
+ * partials of one layer's dkernels and dbias, ceil(B / SATRANS_MMOE_DW_ROW_CHUNK) N (N + 1): 2 B N + that, floats.
+ * The backward WRITES dx [B, N] and both gradients.  No floating-point atomics: equal inputs give equal bits, and a sample's
+ * result row and dx row are the same bits alone as inside a batch. */
+#define SATRANS_CROSS_MAX_LAYERS 8
+#define SATRANS_CROSS_MAX_FEATURES 4096
+#define SATRANS_CROSS_VEC_ROW_CHUNK 32
+typedef struct satrans_cross_desc {
+    int32_t B, N, L;
+    int32_t matrix;                         /* 0: vector form, 1: matrix form */
+    const float* x0;                        /* [B, N] */
+    const float* kernels;                   /* [L, N] or [L, N, N] */
+    const float* bias;                      /* [L, N] */
+} satrans_cross_desc;
+typedef struct satrans_cross_grads {
+    float* kernels;
+    float* bias;
+} satrans_cross_grads;
+int64_t satrans_cross_saved_floats(const satrans_cross_desc* d);
+int64_t satrans_cross_workspace_floats(const satrans_cross_desc* d);
+int satrans_cross_fwd(const satrans_cross_desc* d, float* result, float* saved, void* stream);
+int satrans_cross_bwd(const satrans_cross_desc* d, const float* dresult, float* dx, const float* saved, float* workspace,
+                      const satrans_cross_grads* g, void* stream);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

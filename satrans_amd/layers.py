@@ -31,8 +31,12 @@
     the outer product as a generated operand of the products (csrc/cin.hip); and `XDeepFMHead`, the part of xDeepFM.forward
     behind the embeddings (xdeepfm.py:94-115).  Single-task: nothing is routed.
 
+  * `CrossNet` - deepctr's cross network in its vector and matrix forms, which the reference's DCN calls (models/dcn.py:70,101):
+    the vector form one launch for the whole stack, the matrix form a tile product per layer (csrc/cross.hip); and `DCNHead`,
+    the part of DCN.forward behind the embeddings (dcn.py:90-113).
+
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
-csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip) wrapped in a
+csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip) wrapped in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -1396,4 +1400,172 @@ class XDeepFMHead(nn.Module):
             logit = h if logit is None else logit + h
         if logit is None:
             return self.out.bias.reshape(1, 1).expand(emb.shape[0], 1)
+        return logit + self.out.bias
+
+
+def _cross_desc(x, matrix, kernels, bias):
+    d = N.CrossDesc()
+    d.B, d.N, d.L, d.matrix = x.shape[0], x.shape[1], kernels.shape[0], int(matrix)
+    d.x0, d.kernels, d.bias = x.data_ptr(), kernels.data_ptr(), bias.data_ptr()
+    return d
+
+
+class _CrossFn(torch.autograd.Function):
+    """result [B, N] of the cross network (csrc/cross.hip); kernels [L, N, 1] (vector form) or [L, N, N] (matrix form), bias
+    [L, N, 1].  `saved` is what the backward keeps: [B L] in the vector form, [(2 L - 1) B N] in the matrix form."""
+
+    @staticmethod
+    def forward(ctx, x, matrix, kernels, bias):
+        lib = N.lib()
+        dev = x.device
+        x, kernels, bias = x.contiguous(), kernels.contiguous(), bias.contiguous()
+        d = _cross_desc(x, matrix, kernels, bias)
+        saved = torch.empty(_native_size(lib.satrans_cross_saved_floats, d), dtype=torch.float32, device=dev)
+        result = torch.empty_like(x)
+        N.check(lib.satrans_cross_fwd(C.byref(d), result.data_ptr(), saved.data_ptr(), N.stream_handle(dev)), "satrans_cross_fwd")
+        ctx.matrix = matrix
+        ctx.save_for_backward(x, saved, kernels, bias)
+        ctx.mark_non_differentiable(saved)
+        return result, saved
+
+    @staticmethod
+    def backward(ctx, dresult, _dsaved):
+        lib = N.lib()
+        x, saved, kernels, bias = ctx.saved_tensors
+        d = _cross_desc(x, ctx.matrix, kernels, bias)
+        work = torch.empty(_native_size(lib.satrans_cross_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx, dk, db = torch.empty_like(x), torch.empty_like(kernels), torch.empty_like(bias)
+        g = N.CrossGrads()
+        g.kernels, g.bias = dk.data_ptr(), db.data_ptr()
+        N.check(lib.satrans_cross_bwd(C.byref(d), dresult.contiguous().data_ptr(), dx.data_ptr(), saved.data_ptr(), work.data_ptr(),
+                                      C.byref(g), N.stream_handle(x.device)), "satrans_cross_bwd")
+        return dx, None, dk, db
+
+
+class CrossNet(nn.Module):
+    """deepctr-torch's cross network, which the reference's DCN calls (models/dcn.py:70,101), with deepctr's constructor: `seed`
+    and `device` are accepted and unused.  With x_0 = inputs [B, N]:
+
+        vector:  x_{l+1} = x_0 (x_l . kernels[l]) + bias[l] + x_l               kernels [L, N, 1]
+        matrix:  x_{l+1} = x_0 * (kernels[l] x_l + bias[l]) + x_l               kernels [L, N, N]
+
+    forward(inputs [B, in_features] fp32 on the GPU) -> [B, in_features].  One autograd.Function runs satrans_cross_fwd /
+    satrans_cross_bwd (csrc/cross.hip).  The vector form is one launch for the whole stack each way and keeps B L scalars for the
+    backward, not the layer inputs; the matrix form is a tile product per layer on the exact f32-input MFMA.
+    layer_num = 0 keeps the zero-length parameters and returns the input.
+
+    Parameters are deepctr's, `kernels` and `bias` [L, N, 1], with its initialisation in its order (xavier_normal_ of each
+    kernels[i], zeros for the bias): the `crossnet.*` entries of a reference DCN checkpoint load with load_state_dict.
+    Not built - NotImplementedError at construction: more than CROSS_MAX_LAYERS layers, more than CROSS_MAX_FEATURES features."""
+
+    def __init__(self, in_features, layer_num=2, parameterization='vector', seed=1024, device='cpu'):
+        super().__init__()
+        if parameterization not in ('vector', 'matrix'):
+            raise ValueError("parameterization should be 'vector' or 'matrix'")
+        in_features, layer_num = int(in_features), int(layer_num)
+        if in_features < 1 or layer_num < 0:
+            raise ValueError("CrossNet: in_features must be positive and layer_num non-negative")
+        if layer_num > N.CROSS_MAX_LAYERS:
+            raise NotImplementedError(f"CrossNet: up to {N.CROSS_MAX_LAYERS} layers, got {layer_num}")
+        if in_features > N.CROSS_MAX_FEATURES:
+            raise NotImplementedError(f"CrossNet: up to {N.CROSS_MAX_FEATURES} features, got {in_features}")
+        self.in_features, self.layer_num, self.parameterization = in_features, layer_num, parameterization
+        self.kernels = nn.Parameter(torch.empty(layer_num, in_features, 1 if parameterization == 'vector' else in_features))
+        self.bias = nn.Parameter(torch.empty(layer_num, in_features, 1))
+        for i in range(layer_num):
+            nn.init.xavier_normal_(self.kernels[i])
+        for i in range(layer_num):
+            nn.init.zeros_(self.bias[i])
+
+    def forward(self, inputs):
+        if inputs.dim() != 2 or inputs.shape[1] != self.in_features:
+            raise ValueError(f"CrossNet: expected inputs [B, {self.in_features}], got {tuple(inputs.shape)}")
+        N.require_gpu(inputs, "CrossNet")
+        if inputs.dtype != torch.float32 or self.kernels.dtype != torch.float32:
+            raise TypeError("CrossNet: inputs, parameters and gradients are float32")
+        if self.layer_num == 0:
+            return inputs
+        result, _ = _CrossFn.apply(inputs, self.parameterization == 'matrix', self.kernels, self.bias)
+        return result
+
+
+class DCNHead(nn.Module):
+    """The half of the reference's DCN.forward behind the embedding lookup (models/dcn.py:90-113), with dnn_input =
+    cat(flatten(emb), dense):
+
+        logit = linear_logit + dnn_linear(cat(crossnet(dnn_input), dnn(dnn_input))) + out.bias      (deep & cross)
+                             + dnn_linear(dnn(dnn_input))                                            (cross_num = 0)
+                             + dnn_linear(crossnet(dnn_input))                                       (dnn_hidden_units = ())
+
+    forward(emb [B, field_size, embedding_size] fp32, dense [B, dense_dim] or None, linear_logit [B,1] or None) -> logit [B,1];
+    the caller applies the sigmoid.  The reference's `metatrans` flag (dcn.py:87-88) transforms the embedding block first:
+
+        head = DCNHead(F, D, dense_dim, ...); meta = MetaTransformation(D, num_domains)
+        logit = head(meta(domain_ids, emb), dense, linear_logit)
+
+    The cross network is `CrossNet` above (csrc/cross.hip).  The DNN (Linear + relu layers), `dnn_linear` and the two
+    concatenations are plain torch modules.  At the AliCCP width N = 19 x 32 = 608 with main.py's defaults the DNN is
+    2 (608 x 128 + 128 x 128) = 188 kFLOP per sample and dnn_linear 1.5 k; the vector cross network is 2 layers x 3 N = 3.6 k, so
+    98 % of DCN-V's FLOPs stay in torch - its cross network is memory traffic, not arithmetic.  In DCN-M (2 layers x 2 N^2 =
+    1.48 MFLOP) torch keeps 11 %.  Moving the DNN onto the dense layer launcher of csrc/head_layers.h is the next step.
+
+    Parameter names, shapes, state_dict order and initialisation are the reference DCN's: out.bias (zeros),
+    dnn.linears.{l}.{weight,bias} (weights N(0, init_std)), dnn_linear.weight, crossnet.kernels, crossnet.bias - those entries
+    of a reference checkpoint load with load_state_dict.  Empty dnn_hidden_units leaves no `dnn.*` entries; cross_num = 0
+    keeps the zero-length `crossnet.*` entries, as the reference does.
+
+    regularization_loss() -> [1] is what DCN.__init__ itself adds to the reference's regularization_weight with a non-zero
+    factor, l2_reg_linear sum(dnn_linear.weight^2) + l2_reg_cross sum(crossnet.kernels^2), in get_regularization_loss's
+    arithmetic (main.py leaves both at 1e-5, so a port adds it to its loss).  Not built, as in the other heads: l2_reg_dnn,
+    dropout, batch-norm, activations other than relu."""
+
+    def __init__(self, field_size, embedding_size, dense_dim=0, cross_num=2, cross_parameterization='vector',
+                 dnn_hidden_units=(128, 128), l2_reg_linear=1e-5, l2_reg_cross=1e-5, init_std=0.0001):
+        super().__init__()
+        if field_size < 1 or embedding_size < 1 or dense_dim < 0:
+            raise ValueError("DCNHead: field_size and embedding_size must be positive, dense_dim non-negative")
+        self.field_size, self.embedding_size, self.dense_dim = int(field_size), int(embedding_size), int(dense_dim)
+        units = [int(u) for u in dnn_hidden_units]
+        self.cross_num = int(cross_num)
+        self.use_dnn, self.use_cross = len(units) > 0, self.cross_num > 0
+        if not (self.use_dnn or self.use_cross):
+            raise ValueError("DCNHead: cross_num = 0 with empty dnn_hidden_units leaves no branch")
+        self.l2_reg_linear, self.l2_reg_cross = float(l2_reg_linear), float(l2_reg_cross)
+        n = self.field_size * self.embedding_size + self.dense_dim
+        # (first: in the reference's state_dict `out.*` precedes DCN's own modules, because its BaseModel registers that name)
+        self.out = _OutBias()
+        self.dnn = _TowerDNN(n, units, init_std)
+        self.dnn_linear = nn.Linear((n if self.use_cross else 0) + (units[-1] if self.use_dnn else 0), 1, bias=False)
+        self.crossnet = CrossNet(n, self.cross_num, cross_parameterization)
+
+    def regularization_loss(self):
+        total = torch.zeros((1,), device=self.dnn_linear.weight.device)
+        for p, l2 in ((self.dnn_linear.weight, self.l2_reg_linear), (self.crossnet.kernels, self.l2_reg_cross)):
+            if l2 > 0:
+                total = total + torch.sum(l2 * torch.square(p))
+        return total
+
+    def forward(self, emb, dense=None, linear_logit=None):
+        if emb.dim() != 3 or emb.shape[1] != self.field_size or emb.shape[2] != self.embedding_size:
+            raise ValueError(f"DCNHead: expected emb [B, {self.field_size}, {self.embedding_size}], got {tuple(emb.shape)}")
+        got = 0 if dense is None else (dense.shape[1] if dense.dim() == 2 else -1)
+        if got != self.dense_dim:
+            raise ValueError(f"DCNHead: expected dense [B, {self.dense_dim}], got "
+                             f"{None if dense is None else tuple(dense.shape)}")
+        N.require_gpu(emb, "DCNHead")
+        if emb.dtype != torch.float32:
+            raise TypeError("DCNHead: rows, parameters and gradients are float32")
+        x = torch.flatten(emb, start_dim=1)
+        if dense is not None:
+            x = torch.cat([x, dense], dim=-1)
+        parts = []
+        if self.use_cross:
+            parts.append(self.crossnet(x))
+        if self.use_dnn:
+            h = x
+            for lin in self.dnn.linears:
+                h = torch.relu(lin(h))
+            parts.append(h)
+        h = self.dnn_linear(parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1))
+        logit = h if linear_logit is None else linear_logit + h
         return logit + self.out.bias

@@ -208,6 +208,22 @@ class CINGrads(C.Structure):
     _fields_ = [("w", _vp * CIN_MAX_LAYERS), ("b", _vp * CIN_MAX_LAYERS)]
 
 
+CROSS_MAX_LAYERS = 8          # SATRANS_CROSS_MAX_LAYERS
+CROSS_MAX_FEATURES = 4096     # SATRANS_CROSS_MAX_FEATURES: width of the cross network's rows
+CROSS_VEC_ROW_CHUNK = 32      # SATRANS_CROSS_VEC_ROW_CHUNK: rows that one partial of the vector form's gradients sums
+
+
+class CrossDesc(C.Structure):
+    """Mirror of `satrans_cross_desc`."""
+    _fields_ = [("B", C.c_int32), ("N", C.c_int32), ("L", C.c_int32), ("matrix", C.c_int32), ("x0", _vp), ("kernels", _vp),
+                ("bias", _vp)]
+
+
+class CrossGrads(C.Structure):
+    """Mirror of `satrans_cross_grads`."""
+    _fields_ = [("kernels", _vp), ("bias", _vp)]
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -324,6 +340,10 @@ SIGNATURES = {
     "satrans_cin_workspace_floats": (C.c_int64, [C.POINTER(CINDesc)]),
     "satrans_cin_fwd": (C.c_int, [C.POINTER(CINDesc), _vp, _vp, _vp]),
     "satrans_cin_bwd": (C.c_int, [C.POINTER(CINDesc), _vp, _vp, _vp, _vp, C.POINTER(CINGrads), _vp]),
+    "satrans_cross_saved_floats": (C.c_int64, [C.POINTER(CrossDesc)]),
+    "satrans_cross_workspace_floats": (C.c_int64, [C.POINTER(CrossDesc)]),
+    "satrans_cross_fwd": (C.c_int, [C.POINTER(CrossDesc), _vp, _vp, _vp]),
+    "satrans_cross_bwd": (C.c_int, [C.POINTER(CrossDesc), _vp, _vp, _vp, _vp, C.POINTER(CrossGrads), _vp]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
