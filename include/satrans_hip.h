@@ -42,7 +42,8 @@ extern "C" {
  *    (satrans_adasparse_desc, satrans_adasparse_grads, satrans_adasparse_*), and the scenario-routed SharedBottom head
  *    (satrans_sharedbottom_desc, satrans_sharedbottom_grads, satrans_sharedbottom_*), and xDeepFM's compressed interaction
  *    network (satrans_cin_desc, satrans_cin_grads, satrans_cin_*), and DCN's cross network (satrans_cross_desc,
- *    satrans_cross_grads, satrans_cross_*). */
+ *    satrans_cross_grads, satrans_cross_*), and FiBiNET's SENet, bilinear interaction and head (satrans_senet_*,
+ *    satrans_bilinear_*, satrans_fibinet_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -773,6 +774,93 @@ int64_t satrans_cross_workspace_floats(const satrans_cross_desc* d);
 int satrans_cross_fwd(const satrans_cross_desc* d, float* result, float* saved, void* stream);
 int satrans_cross_bwd(const satrans_cross_desc* d, const float* dresult, float* dx, const float* saved, float* workspace,
                       const satrans_cross_grads* g, void* stream);
+
+/* FiBiNET (deepctr-torch's SENETLayer and BilinearInteraction, which the reference's models/fibinet.py:51-52,93-95 calls, and
+ * the half of its forward behind the lookup).  With e [B, F, D], R = max(1, F / reduction_ratio), pairs (i, j), i < j, in
+ * itertools.combinations order, P = F (F - 1) / 2, pair p = i (2 F - i - 1) / 2 + j - i - 1:
+ *     SENet      z[b,f] = mean_d e[b,f,:]    hid = relu(z w1^T)    a = relu(hid w2^T)    v = e * a[:,:,None]
+ *                w1 [R, F], w2 [F, R] (the excitation's two bias-free Linears)
+ *     bilinear   r_p = (W_w(p) e_i) * e_j    W [nW, D, D] (Linear weights, [d_out, d_in]);  w(p) = 0 (ALL, nW = 1), i (EACH,
+ *                nW = F; the last is never used and its gradient comes out zero), p (INTERACTION, nW = P)
+ *                with a [B, F]:  s_p = a_i a_j r_p, which is the product over v = e * a (one D x D product serves both)
+ *     head       x = [ s_0 .. s_{P-1} | r_0 .. r_{P-1} | dense ]  [B, 2 P D + dense_dim];  hidden layers relu(x W^T + b);
+ *                logit [B, 1] = h dnn_linear_w^T + out_bias
+ * fp32 throughout.  2 to SATRANS_FIBINET_MAX_FIELDS fields, D up to SATRANS_FIBINET_MAX_DIM (any D, not only multiples of 4),
+ * up to SATRANS_MMOE_MAX_HIDDEN hidden layers (none: dnn_linear sits on x), any positive B whose launches fit 2^31 workgroups
+ * (SATRANS_E_UNSUPPORTED beyond); all of that is decided before a device is touched.
+ * satrans_senet_fwd: saved = a [B, F], then hid [B, R]; v [B, F, D] is written when not null.  satrans_senet_bwd takes da
+ * [B, F] and / or dv [B, F, D] (either may be null, not both), ADDS the input gradient into de [B, F, D] and writes g->w1,
+ * g->w2; workspace = 2 ceil(B / SATRANS_FIBINET_SENET_ROW_CHUNK) F R floats.
+ * satrans_bilinear_fwd: out [B, P D] = r, or with d->a: out [B, 2 P D] = [ s | r ].  satrans_bilinear_bwd takes dout and out in
+ * that layout, WRITES de [B, F, D], da [B, F] (with d->a) and dw [nW, D, D]; workspace =
+ * ceil(B / SATRANS_FIBINET_DW_ROW_CHUNK) nW D D floats.
+ * satrans_fibinet_fwd: saved = a, hid, x [B, 2 P D + dense_dim], the hidden rows.  satrans_fibinet_bwd WRITES demb [B, F, D],
+ * ddense [B, dense_dim] (null when dense_dim = 0) and every gradient of g.
+ * No floating-point atomics: equal inputs give equal bits, and a sample's logit and demb row are the same bits alone as
+ * inside a batch. */
+#define SATRANS_FIBINET_MAX_FIELDS 64
+#define SATRANS_FIBINET_MAX_DIM 128
+#define SATRANS_FIBINET_DW_ROW_CHUNK 256
+#define SATRANS_FIBINET_SENET_ROW_CHUNK 32
+#define SATRANS_BILINEAR_ALL 0
+#define SATRANS_BILINEAR_EACH 1
+#define SATRANS_BILINEAR_INTERACTION 2
+typedef struct satrans_senet_desc {
+    int32_t B, F, D, R;
+    const float* e;                         /* [B, F, D] */
+    const float* w1;                        /* [R, F] */
+    const float* w2;                        /* [F, R] */
+} satrans_senet_desc;
+typedef struct satrans_senet_grads {
+    float* w1;
+    float* w2;
+} satrans_senet_grads;
+int64_t satrans_senet_saved_floats(const satrans_senet_desc* d);
+int64_t satrans_senet_workspace_floats(const satrans_senet_desc* d);
+int satrans_senet_fwd(const satrans_senet_desc* d, float* v, float* saved, void* stream);
+int satrans_senet_bwd(const satrans_senet_desc* d, const float* da, const float* dv, const float* saved, float* de, float* workspace,
+                      const satrans_senet_grads* g, void* stream);
+typedef struct satrans_bilinear_desc {
+    int32_t B, F, D;
+    int32_t type;                           /* SATRANS_BILINEAR_* */
+    const float* e;                         /* [B, F, D] */
+    const float* w;                         /* [nW, D, D] */
+    const float* a;                         /* [B, F], or null: the raw block only */
+} satrans_bilinear_desc;
+int64_t satrans_bilinear_workspace_floats(const satrans_bilinear_desc* d);
+int satrans_bilinear_fwd(const satrans_bilinear_desc* d, float* out, void* stream);
+int satrans_bilinear_bwd(const satrans_bilinear_desc* d, const float* dout, const float* out, float* de, float* da, float* workspace,
+                         float* dw, void* stream);
+typedef struct satrans_fibinet_desc {
+    int32_t B, F, D;
+    int32_t type;                           /* SATRANS_BILINEAR_* */
+    int32_t R, dense_dim, n_dnn, reserved;
+    int32_t width[SATRANS_MMOE_MAX_HIDDEN];
+    int32_t reserved2;
+    const float* emb;                       /* [B, F, D] */
+    const float* dense;                     /* [B, dense_dim], null when dense_dim = 0 */
+    const float* se_w1;
+    const float* se_w2;
+    const float* bilinear_w;
+    const float* dnn_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* dnn_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* dnn_linear_w;              /* [1, last width] */
+    const float* out_bias;                  /* [1] */
+} satrans_fibinet_desc;
+typedef struct satrans_fibinet_grads {
+    float* se_w1;
+    float* se_w2;
+    float* bilinear_w;
+    float* dnn_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* dnn_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* dnn_linear_w;
+    float* out_bias;
+} satrans_fibinet_grads;
+int64_t satrans_fibinet_saved_floats(const satrans_fibinet_desc* d);
+int64_t satrans_fibinet_workspace_floats(const satrans_fibinet_desc* d);
+int satrans_fibinet_fwd(const satrans_fibinet_desc* d, float* logit, float* saved, void* stream);
+int satrans_fibinet_bwd(const satrans_fibinet_desc* d, const float* dlogit, float* demb, float* ddense, const float* saved,
+                        float* workspace, const satrans_fibinet_grads* g, void* stream);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

@@ -35,8 +35,13 @@
     the vector form one launch for the whole stack, the matrix form a tile product per layer (csrc/cross.hip); and `DCNHead`,
     the part of DCN.forward behind the embeddings (dcn.py:90-113).
 
+  * `SENETLayer` and `BilinearInteraction` - deepctr's two FiBiNET layers, which the reference's FiBiNET calls
+    (models/fibinet.py:51-52,93-95): the excitation a wave per row, all pairs' bilinear products in one launch; and
+    `FiBiNETHead`, the part of FiBiNET.forward behind the embeddings (fibinet.py:91-112) with its DNN on the dense layer launcher
+    of csrc/head_layers.h, the whole head one autograd.Function (csrc/fibinet.hip).
+
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
-csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip) wrapped in a
+csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip, csrc/fibinet.hip) wrapped in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -1569,3 +1574,308 @@ class DCNHead(nn.Module):
         h = self.dnn_linear(parts[0] if len(parts) == 1 else torch.cat(parts, dim=-1))
         logit = h if linear_logit is None else linear_logit + h
         return logit + self.out.bias
+
+
+def _senet_desc(x, w1, w2):
+    d = N.SENetDesc()
+    d.B, d.F, d.D, d.R = x.shape[0], x.shape[1], x.shape[2], w1.shape[0]
+    d.e, d.w1, d.w2 = x.data_ptr(), w1.data_ptr(), w2.data_ptr()
+    return d
+
+
+class _SENetFn(torch.autograd.Function):
+    """v [B, F, D] = x * a[:, :, None] of the SENet layer (csrc/fibinet.hip); w1 [R, F], w2 [F, R].  `saved` = a [B, F], then the
+    hidden units [B, R]."""
+
+    @staticmethod
+    def forward(ctx, x, w1, w2):
+        lib = N.lib()
+        x, w1, w2 = x.contiguous(), w1.contiguous(), w2.contiguous()
+        d = _senet_desc(x, w1, w2)
+        saved = torch.empty(_native_size(lib.satrans_senet_saved_floats, d), dtype=torch.float32, device=x.device)
+        v = torch.empty_like(x)
+        N.check(lib.satrans_senet_fwd(C.byref(d), v.data_ptr(), saved.data_ptr(), N.stream_handle(x.device)), "satrans_senet_fwd")
+        ctx.save_for_backward(x, saved, w1, w2)
+        ctx.mark_non_differentiable(saved)
+        return v, saved
+
+    @staticmethod
+    def backward(ctx, dv, _dsaved):
+        lib = N.lib()
+        x, saved, w1, w2 = ctx.saved_tensors
+        d = _senet_desc(x, w1, w2)
+        work = torch.empty(_native_size(lib.satrans_senet_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx = torch.zeros_like(x)      # (the backward adds into it)
+        dw1, dw2 = torch.empty_like(w1), torch.empty_like(w2)
+        g = N.SENetGrads()
+        g.w1, g.w2 = dw1.data_ptr(), dw2.data_ptr()
+        N.check(lib.satrans_senet_bwd(C.byref(d), None, dv.contiguous().data_ptr(), saved.data_ptr(), dx.data_ptr(), work.data_ptr(),
+                                      C.byref(g), N.stream_handle(x.device)), "satrans_senet_bwd")
+        return dx, dw1, dw2
+
+
+class SENETLayer(nn.Module):
+    """deepctr-torch's SENET layer, which the reference's FiBiNET calls (models/fibinet.py:51,93), with deepctr's constructor
+    (its spelling `filed_size` included): `seed` and `device` are accepted and unused.  With inputs [B, F, D]:
+
+        Z = mean(inputs, -1);  A = relu(relu(Z W1^T) W2^T);  V = inputs * A[:, :, None]
+
+    forward(inputs [B, filed_size, D] fp32 on the GPU) -> [B, filed_size, D].  One autograd.Function runs satrans_senet_fwd /
+    satrans_senet_bwd (csrc/fibinet.hip): a wave per row each way.  Parameters are deepctr's, `excitation.0.weight` [R, F] and
+    `excitation.2.weight` [F, R], R = max(1, filed_size // reduction_ratio), with torch's Linear default initialisation in
+    deepctr's order.  Not built - NotImplementedError: more than FIBINET_MAX_FIELDS fields (at construction), D beyond
+    FIBINET_MAX_DIM (at the call)."""
+
+    def __init__(self, filed_size, reduction_ratio=3, seed=1024, device='cpu'):
+        super().__init__()
+        filed_size = int(filed_size)
+        if filed_size < 2 or reduction_ratio < 1:
+            raise ValueError("SENETLayer: filed_size must be at least 2 and reduction_ratio at least 1")
+        if filed_size > N.FIBINET_MAX_FIELDS:
+            raise NotImplementedError(f"SENETLayer: up to FIBINET_MAX_FIELDS = {N.FIBINET_MAX_FIELDS} fields, got {filed_size}")
+        self.seed = seed
+        self.filed_size = filed_size
+        self.reduction_size = max(1, filed_size // int(reduction_ratio))
+        self.excitation = nn.Sequential(nn.Linear(self.filed_size, self.reduction_size, bias=False), nn.ReLU(),
+                                        nn.Linear(self.reduction_size, self.filed_size, bias=False), nn.ReLU())
+
+    def forward(self, inputs):
+        if inputs.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs.dim()))
+        if inputs.shape[1] != self.filed_size:
+            raise ValueError(f"SENETLayer: expected inputs [B, {self.filed_size}, D], got {tuple(inputs.shape)}")
+        N.require_gpu(inputs, "SENETLayer")
+        if inputs.dtype != torch.float32 or self.excitation[0].weight.dtype != torch.float32:
+            raise TypeError("SENETLayer: inputs, parameters and gradients are float32")
+        if inputs.shape[2] > N.FIBINET_MAX_DIM:
+            raise NotImplementedError(f"SENETLayer: D up to FIBINET_MAX_DIM = {N.FIBINET_MAX_DIM}, got {inputs.shape[2]}")
+        v, _ = _SENetFn.apply(inputs, self.excitation[0].weight, self.excitation[2].weight)
+        return v
+
+
+def _bilinear_desc(x, kind, w, a=None):
+    d = N.BilinearDesc()
+    d.B, d.F, d.D, d.type = x.shape[0], x.shape[1], x.shape[2], kind
+    d.e, d.w, d.a = x.data_ptr(), w.data_ptr(), None if a is None else a.data_ptr()
+    return d
+
+
+class _BilinearFn(torch.autograd.Function):
+    """out [B, P, D] of the bilinear interaction (csrc/fibinet.hip); `weights`: the Linear weights [D, D] in deepctr's order."""
+
+    @staticmethod
+    def forward(ctx, x, kind, *weights):
+        lib = N.lib()
+        x = x.contiguous()
+        w = torch.stack(weights)
+        F = x.shape[1]
+        out = torch.empty(x.shape[0], F * (F - 1) // 2, x.shape[2], dtype=torch.float32, device=x.device)
+        N.check(lib.satrans_bilinear_fwd(C.byref(_bilinear_desc(x, kind, w)), out.data_ptr(), N.stream_handle(x.device)),
+                "satrans_bilinear_fwd")
+        ctx.kind = kind
+        ctx.save_for_backward(x, w, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = N.lib()
+        x, w, out = ctx.saved_tensors
+        d = _bilinear_desc(x, ctx.kind, w)
+        work = torch.empty(_native_size(lib.satrans_bilinear_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx, dw = torch.empty_like(x), torch.empty_like(w)
+        N.check(lib.satrans_bilinear_bwd(C.byref(d), dout.contiguous().data_ptr(), out.data_ptr(), dx.data_ptr(), None, work.data_ptr(),
+                                         dw.data_ptr(), N.stream_handle(x.device)), "satrans_bilinear_bwd")
+        return (dx, None, *dw.unbind(0))
+
+
+def _bilinear_modules(filed_size, embedding_size, bilinear_type):
+    """deepctr's `bilinear` attribute: one Linear ('all'), one per field ('each'), one per pair ('interaction')."""
+    if bilinear_type == "all":
+        return nn.Linear(embedding_size, embedding_size, bias=False)
+    if bilinear_type == "each":
+        return nn.ModuleList([nn.Linear(embedding_size, embedding_size, bias=False) for _ in range(filed_size)])
+    if bilinear_type == "interaction":
+        return nn.ModuleList([nn.Linear(embedding_size, embedding_size, bias=False)
+                              for _ in range(filed_size * (filed_size - 1) // 2)])
+    raise NotImplementedError
+
+
+class BilinearInteraction(nn.Module):
+    """deepctr-torch's bilinear interaction, which the reference's FiBiNET calls (models/fibinet.py:52,94-95), with deepctr's
+    constructor: `seed` and `device` are accepted and unused.  For the pairs (i, j), i < j, in itertools.combinations order:
+
+        'all'          bilinear(x_i) * x_j               one Linear(D, D, bias=False), `bilinear.weight`
+        'each'         bilinear[i](x_i) * x_j            one per field, `bilinear.{i}.weight`; the last is never used and its
+                                                         gradient is zero
+        'interaction'  bilinear[p](x_i) * x_j            one per pair, `bilinear.{p}.weight`
+
+    forward(inputs [B, filed_size, embedding_size] fp32 on the GPU) -> [B, P, embedding_size], P = F (F - 1) / 2.  One
+    autograd.Function runs satrans_bilinear_fwd / satrans_bilinear_bwd (csrc/fibinet.hip): all pairs in one launch on the exact
+    f32-input MFMA; the backward recomputes bilinear(x_i) instead of keeping it.  Parameters have deepctr's names, shapes,
+    order and initialisation.  An unknown type raises NotImplementedError, as deepctr does; so do more than
+    FIBINET_MAX_FIELDS fields and an embedding size beyond FIBINET_MAX_DIM."""
+
+    def __init__(self, filed_size, embedding_size, bilinear_type="interaction", seed=1024, device='cpu'):
+        super().__init__()
+        filed_size, embedding_size = int(filed_size), int(embedding_size)
+        if bilinear_type not in N.BILINEAR_TYPES:
+            raise NotImplementedError
+        if filed_size < 2 or embedding_size < 1:
+            raise ValueError("BilinearInteraction: filed_size must be at least 2 and embedding_size positive")
+        if filed_size > N.FIBINET_MAX_FIELDS:
+            raise NotImplementedError(f"BilinearInteraction: up to FIBINET_MAX_FIELDS = {N.FIBINET_MAX_FIELDS} fields, got {filed_size}")
+        if embedding_size > N.FIBINET_MAX_DIM:
+            raise NotImplementedError(f"BilinearInteraction: embedding_size up to FIBINET_MAX_DIM = {N.FIBINET_MAX_DIM}, got "
+                                      f"{embedding_size}")
+        self.bilinear_type, self.seed = bilinear_type, seed
+        self.filed_size, self.embedding_size = filed_size, embedding_size
+        self.bilinear = _bilinear_modules(filed_size, embedding_size, bilinear_type)
+
+    def weights(self):
+        return [self.bilinear.weight] if self.bilinear_type == "all" else [m.weight for m in self.bilinear]
+
+    def forward(self, inputs):
+        if inputs.dim() != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (inputs.dim()))
+        if inputs.shape[1] != self.filed_size or inputs.shape[2] != self.embedding_size:
+            raise ValueError(f"BilinearInteraction: expected inputs [B, {self.filed_size}, {self.embedding_size}], got "
+                             f"{tuple(inputs.shape)}")
+        N.require_gpu(inputs, "BilinearInteraction")
+        if inputs.dtype != torch.float32 or self.weights()[0].dtype != torch.float32:
+            raise TypeError("BilinearInteraction: inputs, parameters and gradients are float32")
+        return _BilinearFn.apply(inputs, N.BILINEAR_TYPES[self.bilinear_type], *self.weights())
+
+
+def _fibinet_fill(tgt, n_dnn, se_w1, se_w2, bil_w, dnn, dnn_linear_w, out_bias):
+    """Set the parameter pointers of a satrans_fibinet_desc / satrans_fibinet_grads; `dnn`: the weights, then the biases."""
+    tgt.se_w1, tgt.se_w2, tgt.bilinear_w = se_w1.data_ptr(), se_w2.data_ptr(), bil_w.data_ptr()
+    for l in range(n_dnn):
+        tgt.dnn_w[l], tgt.dnn_b[l] = dnn[l].data_ptr(), dnn[n_dnn + l].data_ptr()
+    tgt.dnn_linear_w, tgt.out_bias = dnn_linear_w.data_ptr(), out_bias.data_ptr()
+    return tgt
+
+
+def _fibinet_desc(emb, dense, kind, se_w1, se_w2, bil_w, dnn, dnn_linear_w, out_bias):
+    n_dnn = len(dnn) // 2
+    d = _fibinet_fill(N.FiBiNETDesc(), n_dnn, se_w1, se_w2, bil_w, dnn, dnn_linear_w, out_bias)
+    d.B, d.F, d.D, d.type, d.R = emb.shape[0], emb.shape[1], emb.shape[2], kind, se_w1.shape[0]
+    d.dense_dim, d.n_dnn = 0 if dense is None else dense.shape[1], n_dnn
+    for l in range(n_dnn):
+        d.width[l] = dnn[l].shape[0]
+    d.emb, d.dense = emb.data_ptr(), None if dense is None else dense.data_ptr()
+    return d
+
+
+class _FiBiNETFn(torch.autograd.Function):
+    """logit [B, 1] of the FiBiNET head (csrc/fibinet.hip).  `tensors`: se_w1, se_w2, the n_bil bilinear weights, the DNN's
+    weights, its biases, dnn_linear's weight, out.bias.  `saved` = a, the hidden units, the DNN input, the DNN's hidden rows."""
+
+    @staticmethod
+    def forward(ctx, emb, dense, kind, n_bil, *tensors):
+        lib = N.lib()
+        dev = emb.device
+        emb = emb.contiguous()
+        dense = None if dense is None else dense.contiguous()
+        se_w1, se_w2 = tensors[0].contiguous(), tensors[1].contiguous()
+        bil_w = torch.stack(tensors[2:2 + n_bil])
+        dnn = tuple(t.contiguous() for t in tensors[2 + n_bil:-2])
+        dnn_linear_w, out_bias = tensors[-2].contiguous(), tensors[-1].contiguous()
+        d = _fibinet_desc(emb, dense, kind, se_w1, se_w2, bil_w, dnn, dnn_linear_w, out_bias)
+        saved = torch.empty(_native_size(lib.satrans_fibinet_saved_floats, d), dtype=torch.float32, device=dev)
+        logit = torch.empty(emb.shape[0], 1, dtype=torch.float32, device=dev)
+        N.check(lib.satrans_fibinet_fwd(C.byref(d), logit.data_ptr(), saved.data_ptr(), N.stream_handle(dev)), "satrans_fibinet_fwd")
+        ctx.kind, ctx.has_dense = kind, dense is not None
+        ctx.save_for_backward(emb, saved, se_w1, se_w2, bil_w, dnn_linear_w, out_bias, *dnn, *(() if dense is None else (dense,)))
+        ctx.mark_non_differentiable(saved)
+        return logit, saved
+
+    @staticmethod
+    def backward(ctx, dlogit, _dsaved):
+        lib = N.lib()
+        emb, saved, se_w1, se_w2, bil_w, dnn_linear_w, out_bias, *rest = ctx.saved_tensors
+        dense = rest.pop() if ctx.has_dense else None
+        dnn = tuple(rest)
+        d = _fibinet_desc(emb, dense, ctx.kind, se_w1, se_w2, bil_w, dnn, dnn_linear_w, out_bias)
+        work = torch.empty(_native_size(lib.satrans_fibinet_workspace_floats, d), dtype=torch.float32, device=emb.device)
+        demb = torch.empty_like(emb)
+        ddense = None if dense is None else torch.empty_like(dense)
+        grads = [torch.empty_like(t) for t in (se_w1, se_w2, bil_w, *dnn, dnn_linear_w, out_bias)]
+        g = _fibinet_fill(N.FiBiNETGrads(), len(dnn) // 2, grads[0], grads[1], grads[2], grads[3:-2], grads[-2], grads[-1])
+        N.check(lib.satrans_fibinet_bwd(C.byref(d), dlogit.contiguous().data_ptr(), demb.data_ptr(),
+                                        None if ddense is None else ddense.data_ptr(), saved.data_ptr(), work.data_ptr(), C.byref(g),
+                                        N.stream_handle(emb.device)), "satrans_fibinet_bwd")
+        return (demb, ddense, None, None, grads[0], grads[1], *grads[2].unbind(0), *grads[3:])
+
+
+class FiBiNETHead(nn.Module):
+    """The half of the reference's FiBiNET.forward behind the embedding lookup (models/fibinet.py:91-112):
+
+        S = Bilinear(SE(emb));  R = Bilinear(emb);  dnn_input = cat(flatten(cat(S, R, dim=1)), dense)
+        logit = linear_logit + dnn_linear(dnn(dnn_input)) + out.bias
+
+    forward(emb [B, field_size, embedding_size] fp32, dense [B, dense_dim] or None, linear_logit [B,1] or None) -> logit [B,1];
+    the caller applies the sigmoid.  `emb` is the concatenation of the looked-up embeddings of ALL sparse fields in field order,
+    the domain column included; the reference's `metatrans` flag (fibinet.py:83-86) transforms that block first:
+
+        head = FiBiNETHead(F, D, dense_dim, ...); meta = MetaTransformation(D, num_domains)
+        logit = head(meta(domain_ids, emb), dense, linear_logit)
+
+    The whole head is ONE autograd.Function over satrans_fibinet_fwd / satrans_fibinet_bwd (csrc/fibinet.hip): the excitation,
+    both bilinear blocks from one D x D product per pair written straight into the DNN input, and the DNN itself - the widest of
+    any baseline, [B, F (F - 1) D + dense_dim] - on the dense layer launcher of csrc/head_layers.h.  linear_logit is added
+    outside it.  Empty dnn_hidden_units puts dnn_linear directly on the DNN input.
+
+    Parameter names, shapes, state_dict order and initialisation are the reference FiBiNET's: out.bias (zeros),
+    SE.excitation.{0,2}.weight, Bilinear.bilinear[.{i}].weight, dnn.linears.{l}.{weight,bias} (weights N(0, init_std)),
+    dnn_linear.weight - those entries of a reference checkpoint load with load_state_dict.  An unused 'each' weight gets a
+    zero gradient (the reference leaves it None).
+    regularization_loss() -> [1] is what FiBiNET.__init__ itself adds to the reference's regularization_weight: nothing.
+    The reference's fibinet.py has no add_regularization_weight call (the recorded runs pin that), so the result is zero;
+    `l2_reg_linear` is accepted as the reference's constructor accepts it, where it reaches BaseModel's linear model only.
+    Not built: a FiBiNET model class behind BaseModel; dropout, batch-norm and activations other than relu in the DNN
+    (NotImplementedError); bf16; more than MMOE_MAX_HIDDEN hidden layers, FIBINET_MAX_FIELDS fields, an embedding size beyond
+    FIBINET_MAX_DIM (NotImplementedError at construction)."""
+
+    def __init__(self, field_size, embedding_size, dense_dim=0, bilinear_type='interaction', reduction_ratio=3,
+                 dnn_hidden_units=(128, 128), l2_reg_linear=1e-5, init_std=0.0001, dnn_dropout=0, dnn_activation='relu',
+                 dnn_use_bn=False):
+        super().__init__()
+        if bilinear_type not in N.BILINEAR_TYPES:
+            raise NotImplementedError
+        if field_size < 2:
+            raise ValueError("FiBiNETHead: field_size must be at least 2 (one pair)")
+        if embedding_size < 1 or dense_dim < 0 or reduction_ratio < 1:
+            raise ValueError("FiBiNETHead: embedding_size must be positive, dense_dim non-negative, reduction_ratio at least 1")
+        if dnn_dropout != 0 or dnn_use_bn or dnn_activation != 'relu':
+            raise NotImplementedError("FiBiNETHead: dropout, batch-norm and activations other than relu are not built")
+        units = [int(u) for u in dnn_hidden_units]
+        if len(units) > N.MMOE_MAX_HIDDEN:
+            raise NotImplementedError(f"FiBiNETHead: up to MMOE_MAX_HIDDEN = {N.MMOE_MAX_HIDDEN} hidden layers, got {len(units)}")
+        self.field_size, self.embedding_size, self.dense_dim = int(field_size), int(embedding_size), int(dense_dim)
+        self.bilinear_type, self.l2_reg_linear = bilinear_type, float(l2_reg_linear)
+        n = self.field_size * (self.field_size - 1) * self.embedding_size + self.dense_dim
+        # (first: in the reference's state_dict `out.*` precedes FiBiNET's own modules, because its BaseModel registers that name)
+        self.out = _OutBias()
+        self.SE = SENETLayer(self.field_size, reduction_ratio)
+        self.Bilinear = BilinearInteraction(self.field_size, self.embedding_size, bilinear_type)
+        self.dnn = _TowerDNN(n, units, init_std)
+        self.dnn_linear = nn.Linear(units[-1] if units else n, 1, bias=False)
+
+    def regularization_loss(self):
+        return torch.zeros((1,), device=self.dnn_linear.weight.device)
+
+    def forward(self, emb, dense=None, linear_logit=None):
+        if emb.dim() != 3 or emb.shape[1] != self.field_size or emb.shape[2] != self.embedding_size:
+            raise ValueError(f"FiBiNETHead: expected emb [B, {self.field_size}, {self.embedding_size}], got {tuple(emb.shape)}")
+        got = 0 if dense is None else (dense.shape[1] if dense.dim() == 2 else -1)
+        if got != self.dense_dim:
+            raise ValueError(f"FiBiNETHead: expected dense [B, {self.dense_dim}], got "
+                             f"{None if dense is None else tuple(dense.shape)}")
+        N.require_gpu(emb, "FiBiNETHead")
+        if emb.dtype != torch.float32 or self.dnn_linear.weight.dtype != torch.float32:
+            raise TypeError("FiBiNETHead: rows, parameters and gradients are float32")
+        bil = self.Bilinear.weights()
+        tensors = ([self.SE.excitation[0].weight, self.SE.excitation[2].weight] + bil + [lin.weight for lin in self.dnn.linears] +
+                   [lin.bias for lin in self.dnn.linears] + [self.dnn_linear.weight, self.out.bias])
+        logit, _ = _FiBiNETFn.apply(emb, dense if self.dense_dim else None, N.BILINEAR_TYPES[self.bilinear_type], len(bil), *tensors)
+        return logit if linear_logit is None else linear_logit + logit

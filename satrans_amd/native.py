@@ -224,6 +224,47 @@ class CrossGrads(C.Structure):
     _fields_ = [("kernels", _vp), ("bias", _vp)]
 
 
+FIBINET_MAX_FIELDS = 64          # SATRANS_FIBINET_MAX_FIELDS
+FIBINET_MAX_DIM = 128            # SATRANS_FIBINET_MAX_DIM: the embedding size
+FIBINET_DW_ROW_CHUNK = 256       # SATRANS_FIBINET_DW_ROW_CHUNK: rows that one partial of the bilinear weight gradients sums
+FIBINET_SENET_ROW_CHUNK = 32     # SATRANS_FIBINET_SENET_ROW_CHUNK: rows that one partial of the excitation's gradients sums
+BILINEAR_ALL, BILINEAR_EACH, BILINEAR_INTERACTION = 0, 1, 2      # SATRANS_BILINEAR_*
+BILINEAR_TYPES = {"all": BILINEAR_ALL, "each": BILINEAR_EACH, "interaction": BILINEAR_INTERACTION}
+
+
+class SENetDesc(C.Structure):
+    """Mirror of `satrans_senet_desc`."""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("R", C.c_int32), ("e", _vp), ("w1", _vp), ("w2", _vp)]
+
+
+class SENetGrads(C.Structure):
+    """Mirror of `satrans_senet_grads`."""
+    _fields_ = [("w1", _vp), ("w2", _vp)]
+
+
+class BilinearDesc(C.Structure):
+    """Mirror of `satrans_bilinear_desc`."""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("type", C.c_int32), ("e", _vp), ("w", _vp), ("a", _vp)]
+
+
+# the parameter pointers of satrans_fibinet_desc / satrans_fibinet_grads in the header's order: (name, per hidden layer)
+FIBINET_POINTERS = (("se_w1", False), ("se_w2", False), ("bilinear_w", False), ("dnn_w", True), ("dnn_b", True),
+                    ("dnn_linear_w", False), ("out_bias", False))
+_FIBINET_POINTER_FIELDS = [(name, _vp * MMOE_MAX_HIDDEN if per_layer else _vp) for name, per_layer in FIBINET_POINTERS]
+
+
+class FiBiNETDesc(C.Structure):
+    """Mirror of `satrans_fibinet_desc` (the DNN's layer limit is the MMoE head's: MMOE_MAX_HIDDEN)."""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("type", C.c_int32), ("R", C.c_int32),
+                ("dense_dim", C.c_int32), ("n_dnn", C.c_int32), ("reserved", C.c_int32), ("width", C.c_int32 * MMOE_MAX_HIDDEN),
+                ("reserved2", C.c_int32), ("emb", _vp), ("dense", _vp)] + _FIBINET_POINTER_FIELDS
+
+
+class FiBiNETGrads(C.Structure):
+    """Mirror of `satrans_fibinet_grads`."""
+    _fields_ = list(_FIBINET_POINTER_FIELDS)
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -344,6 +385,17 @@ SIGNATURES = {
     "satrans_cross_workspace_floats": (C.c_int64, [C.POINTER(CrossDesc)]),
     "satrans_cross_fwd": (C.c_int, [C.POINTER(CrossDesc), _vp, _vp, _vp]),
     "satrans_cross_bwd": (C.c_int, [C.POINTER(CrossDesc), _vp, _vp, _vp, _vp, C.POINTER(CrossGrads), _vp]),
+    "satrans_senet_saved_floats": (C.c_int64, [C.POINTER(SENetDesc)]),
+    "satrans_senet_workspace_floats": (C.c_int64, [C.POINTER(SENetDesc)]),
+    "satrans_senet_fwd": (C.c_int, [C.POINTER(SENetDesc), _vp, _vp, _vp]),
+    "satrans_senet_bwd": (C.c_int, [C.POINTER(SENetDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(SENetGrads), _vp]),
+    "satrans_bilinear_workspace_floats": (C.c_int64, [C.POINTER(BilinearDesc)]),
+    "satrans_bilinear_fwd": (C.c_int, [C.POINTER(BilinearDesc), _vp, _vp]),
+    "satrans_bilinear_bwd": (C.c_int, [C.POINTER(BilinearDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "satrans_fibinet_saved_floats": (C.c_int64, [C.POINTER(FiBiNETDesc)]),
+    "satrans_fibinet_workspace_floats": (C.c_int64, [C.POINTER(FiBiNETDesc)]),
+    "satrans_fibinet_fwd": (C.c_int, [C.POINTER(FiBiNETDesc), _vp, _vp, _vp]),
+    "satrans_fibinet_bwd": (C.c_int, [C.POINTER(FiBiNETDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(FiBiNETGrads), _vp]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
