@@ -43,7 +43,8 @@ extern "C" {
  *    (satrans_sharedbottom_desc, satrans_sharedbottom_grads, satrans_sharedbottom_*), and xDeepFM's compressed interaction
  *    network (satrans_cin_desc, satrans_cin_grads, satrans_cin_*), and DCN's cross network (satrans_cross_desc,
  *    satrans_cross_grads, satrans_cross_*), and FiBiNET's SENet, bilinear interaction and head (satrans_senet_*,
- *    satrans_bilinear_*, satrans_fibinet_*). */
+ *    satrans_bilinear_*, satrans_fibinet_*), and PNN's inner and outer product layers and head (satrans_inner_product_*,
+ *    satrans_outer_product_*, satrans_pnn_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -861,6 +862,81 @@ int64_t satrans_fibinet_workspace_floats(const satrans_fibinet_desc* d);
 int satrans_fibinet_fwd(const satrans_fibinet_desc* d, float* logit, float* saved, void* stream);
 int satrans_fibinet_bwd(const satrans_fibinet_desc* d, const float* dlogit, float* demb, float* ddense, const float* saved,
                         float* workspace, const satrans_fibinet_grads* g, void* stream);
+
+/* PNN (deepctr-torch's InnerProductLayer and OutterProductLayer, which the reference's models/pnn.py:14,61,65 calls, and
+ * pnn.py:91-114).  With e [B, F, D], pairs (i, j), i < j, in itertools.combinations order, P = F (F - 1) / 2, pair
+ * p = i (2 F - i - 1) / 2 + j - i - 1:
+ *     inner        ip[b,p] = sum_d e_i[d] e_j[d]
+ *     outer MAT    op[b,p] = sum_n ( sum_k e_i[k] kernel[n,p,k] ) e_j[n]          kernel [D, P, D]
+ *     outer VEC    op[b,p] = sum_d e_i[d] e_j[d] kernel[p,d]                      kernel [P, D]
+ *     outer NUM    op[b,p] = kernel[p,0] * sum_d e_i[d] e_j[d]                    kernel [P, 1]
+ *     head         x = [ flatten(e) (F D) | ip (P, if use_inner) | op (P, if use_outer) | dense ];  hidden layers
+ *                  relu(x W^T + b);  logit [B, 1] = h dnn_linear_w^T + out_bias
+ * Backward, with g_p[b] the upstream gradient of one product column:
+ *     inner / NUM / VEC   de_i += g_p c_p * e_j,  de_j += g_p c_p * e_i;  c_p = 1 (inner), kernel[p] (NUM), kernel[p,:] (VEC);
+ *                         dkernel[p] = sum_b g_p <e_i, e_j> (NUM);  dkernel[p,d] = sum_b g_p e_i[d] e_j[d] (VEC)
+ *     MAT                 de_j += K_p (g_p e_i),  de_i += K_p^T (g_p e_j),  dkernel[n,p,k] = sum_b g_p e_j[n] e_i[k]
+ *                         (K_p = kernel[:, p, :], read in place: row n at kernel + (n P + p) D)
+ * fp32 throughout.  2 to SATRANS_PNN_MAX_FIELDS fields, D up to SATRANS_PNN_MAX_DIM (any D, not only multiples of 4), up to
+ * SATRANS_MMOE_MAX_HIDDEN hidden layers (none: dnn_linear sits on x), any positive B whose launches fit 2^31 workgroups
+ * (SATRANS_E_UNSUPPORTED beyond); all of that is decided before a device is touched.
+ * satrans_inner_product_fwd: out [B, P].  satrans_inner_product_bwd takes dout [B, P] and WRITES de [B, F, D].
+ * satrans_outer_product_fwd: out [B, P].  satrans_outer_product_bwd takes dout [B, P] and WRITES de [B, F, D] and dkernel (the
+ * kernel's shape); workspace = ceil(B / SATRANS_PNN_DW_ROW_CHUNK) P D floats times D (MAT) or 1 (VEC, NUM).
+ * satrans_pnn_fwd: saved = x [B, F D + P use_inner + P use_outer + dense_dim], the hidden rows.  satrans_pnn_bwd WRITES demb
+ * [B, F, D], ddense [B, dense_dim] (null when dense_dim = 0) and every gradient of g (g->kernel and d->kernel may be null
+ * without use_outer).  With neither product the head is the DNN over [ flatten(e) | dense ].
+ * No floating-point atomics: equal inputs give equal bits, and a sample's logit and demb row are the same bits alone as
+ * inside a batch. */
+#define SATRANS_PNN_MAX_FIELDS 64
+#define SATRANS_PNN_MAX_DIM 128
+#define SATRANS_PNN_DW_ROW_CHUNK 256
+#define SATRANS_PNN_KERNEL_MAT 0
+#define SATRANS_PNN_KERNEL_VEC 1
+#define SATRANS_PNN_KERNEL_NUM 2
+typedef struct satrans_inner_product_desc {
+    int32_t B, F, D, reserved;
+    const float* e;                         /* [B, F, D] */
+} satrans_inner_product_desc;
+int satrans_inner_product_fwd(const satrans_inner_product_desc* d, float* out, void* stream);
+int satrans_inner_product_bwd(const satrans_inner_product_desc* d, const float* dout, float* de, void* stream);
+typedef struct satrans_outer_product_desc {
+    int32_t B, F, D;
+    int32_t kernel_type;                    /* SATRANS_PNN_KERNEL_* */
+    const float* e;                         /* [B, F, D] */
+    const float* kernel;                    /* [D, P, D] (MAT), [P, D] (VEC), [P, 1] (NUM) */
+} satrans_outer_product_desc;
+int64_t satrans_outer_product_workspace_floats(const satrans_outer_product_desc* d);
+int satrans_outer_product_fwd(const satrans_outer_product_desc* d, float* out, void* stream);
+int satrans_outer_product_bwd(const satrans_outer_product_desc* d, const float* dout, float* de, float* workspace, float* dkernel,
+                              void* stream);
+typedef struct satrans_pnn_desc {
+    int32_t B, F, D;
+    int32_t use_inner, use_outer;
+    int32_t kernel_type;                    /* SATRANS_PNN_KERNEL_* (read with use_outer) */
+    int32_t dense_dim, n_dnn;
+    int32_t width[SATRANS_MMOE_MAX_HIDDEN];
+    int32_t reserved;
+    const float* emb;                       /* [B, F, D] */
+    const float* dense;                     /* [B, dense_dim], null when dense_dim = 0 */
+    const float* kernel;                    /* the outer product's, null without use_outer */
+    const float* dnn_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* dnn_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* dnn_linear_w;              /* [1, last width] */
+    const float* out_bias;                  /* [1] */
+} satrans_pnn_desc;
+typedef struct satrans_pnn_grads {
+    float* kernel;
+    float* dnn_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* dnn_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* dnn_linear_w;
+    float* out_bias;
+} satrans_pnn_grads;
+int64_t satrans_pnn_saved_floats(const satrans_pnn_desc* d);
+int64_t satrans_pnn_workspace_floats(const satrans_pnn_desc* d);
+int satrans_pnn_fwd(const satrans_pnn_desc* d, float* logit, float* saved, void* stream);
+int satrans_pnn_bwd(const satrans_pnn_desc* d, const float* dlogit, float* demb, float* ddense, const float* saved, float* workspace,
+                    const satrans_pnn_grads* g, void* stream);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

@@ -4,11 +4,12 @@ from .inputs import DenseFeat, SparseFeat, VarLenSparseFeat, build_input_feature
 from .callbacks import History  # noqa: F401
 from .basemodel import BaseModel  # noqa: F401
 from .satrans import SATrans  # noqa: F401
-from .layers import (CIN, AdaSparseHead, BilinearInteraction, CrossNet, DCNHead, FiBiNETHead, MDR_BatchNorm,  # noqa: F401
-                     MetaTransformation, MMoEHead, PartitionedNorm, PLEHead, PrunedDNN, SelfAttention_Layer, SENETLayer,
-                     SharedBottomHead, StarHead, StarTowers, XDeepFMHead)
+from .layers import (CIN, AdaSparseHead, BilinearInteraction, CrossNet, DCNHead, FiBiNETHead, InnerProductLayer,  # noqa: F401
+                     MDR_BatchNorm, MetaTransformation, MMoEHead, OutterProductLayer, PartitionedNorm, PLEHead, PNNHead, PrunedDNN,
+                     SelfAttention_Layer, SENETLayer, SharedBottomHead, StarHead, StarTowers, XDeepFMHead)
 
 __all__ = ["SATrans", "BaseModel", "SparseFeat", "DenseFeat", "VarLenSparseFeat", "get_feature_names",
            "build_input_features", "History", "SelfAttention_Layer", "MetaTransformation",
            "MDR_BatchNorm", "PartitionedNorm", "StarTowers", "StarHead", "MMoEHead", "PLEHead", "PrunedDNN", "AdaSparseHead",
-           "SharedBottomHead", "CIN", "XDeepFMHead", "CrossNet", "DCNHead", "SENETLayer", "BilinearInteraction", "FiBiNETHead"]
+           "SharedBottomHead", "CIN", "XDeepFMHead", "CrossNet", "DCNHead", "SENETLayer", "BilinearInteraction", "FiBiNETHead",
+           "InnerProductLayer", "OutterProductLayer", "PNNHead"]

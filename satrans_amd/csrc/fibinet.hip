@@ -34,6 +34,7 @@
 // out.bias as that layer's bias, so d out.bias falls out of the same launches.
 // No floating-point atomics; every sum has a fixed order; a row's results do not depend on its place in a tile.  fp32 only.
 #include "head_layers.h"
+#include "pair_index.h"
 
 namespace satrans {
 namespace {
@@ -50,17 +51,6 @@ __device__ __forceinline__ float fib_wave_sum(float v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
-}
-
-__device__ __forceinline__ int pair_index(int i, int j, int F) { return i * (2 * F - i - 1) / 2 + j - i - 1; }
-
-__device__ __forceinline__ void pair_fields(int p, int F, int& i, int& j) {
-    i = 0;
-    while (p >= F - 1 - i) {
-        p -= F - 1 - i;
-        ++i;
-    }
-    j = i + 1 + p;
 }
 
 __device__ __forceinline__ int weight_of(int type, int i, int p) {

@@ -40,8 +40,14 @@
     `FiBiNETHead`, the part of FiBiNET.forward behind the embeddings (fibinet.py:91-112) with its DNN on the dense layer launcher
     of csrc/head_layers.h, the whole head one autograd.Function (csrc/fibinet.hip).
 
+  * `InnerProductLayer` and `OutterProductLayer` - deepctr's two PNN layers, which the reference's PNN calls
+    (models/pnn.py:61,65,94-99): a row read once for all of its inner, 'vec' and 'num' products, the 'mat' outer product one
+    D x D product per pair on the matrix pipe reduced inside the workgroup; and `PNNHead`, the part of PNN.forward behind the
+    embeddings (pnn.py:91-114), the whole head one autograd.Function (csrc/pnn.hip).
+
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
-csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip, csrc/fibinet.hip) wrapped in a
+csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip, csrc/fibinet.hip, csrc/pnn.hip) wrapped
+in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
 from __future__ import annotations
@@ -1879,3 +1885,297 @@ class FiBiNETHead(nn.Module):
                    [lin.bias for lin in self.dnn.linears] + [self.dnn_linear.weight, self.out.bias])
         logit, _ = _FiBiNETFn.apply(emb, dense if self.dense_dim else None, N.BILINEAR_TYPES[self.bilinear_type], len(bil), *tensors)
         return logit if linear_logit is None else linear_logit + logit
+
+
+def _pieces(inputs, what):
+    """[B, F, D] of deepctr's list of [B, 1, D] pieces (or of a [B, F, D] tensor as it is)."""
+    x = torch.cat(list(inputs), dim=1) if isinstance(inputs, (list, tuple)) else inputs
+    if x.dim() != 3 or x.shape[1] < 2:
+        raise ValueError(f"{what}: expected [B, F, D] with F >= 2 or a list of [B, 1, D] pieces, got {tuple(x.shape)}")
+    N.require_gpu(x, what)
+    if x.dtype != torch.float32:
+        raise TypeError(f"{what}: inputs, parameters and gradients are float32")
+    if x.shape[1] > N.PNN_MAX_FIELDS or x.shape[2] > N.PNN_MAX_DIM:
+        raise NotImplementedError(f"{what}: up to PNN_MAX_FIELDS = {N.PNN_MAX_FIELDS} fields and D up to PNN_MAX_DIM = "
+                                  f"{N.PNN_MAX_DIM}, got {tuple(x.shape)}")
+    return x
+
+
+def _inner_desc(x):
+    d = N.InnerProductDesc()
+    d.B, d.F, d.D, d.e = x.shape[0], x.shape[1], x.shape[2], x.data_ptr()
+    return d
+
+
+class _InnerProductFn(torch.autograd.Function):
+    """out [B, P] = <x_i, x_j> over the pairs (csrc/pnn.hip)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        F = x.shape[1]
+        out = torch.empty(x.shape[0], F * (F - 1) // 2, dtype=torch.float32, device=x.device)
+        N.check(N.lib().satrans_inner_product_fwd(C.byref(_inner_desc(x)), out.data_ptr(), N.stream_handle(x.device)),
+                "satrans_inner_product_fwd")
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, = ctx.saved_tensors
+        dx = torch.empty_like(x)
+        N.check(N.lib().satrans_inner_product_bwd(C.byref(_inner_desc(x)), dout.contiguous().data_ptr(), dx.data_ptr(),
+                                                  N.stream_handle(x.device)), "satrans_inner_product_bwd")
+        return dx
+
+
+class InnerProductLayer(nn.Module):
+    """deepctr-torch's inner product layer, which the reference's PNN calls (models/pnn.py:61,95-96), with deepctr's constructor
+    (`device` is accepted and unused).  For the pairs (i, j), i < j, in the order of deepctr's double loop:
+
+        out[b, p, 0] = sum_d x_i[b, d] x_j[b, d]
+
+    forward(inputs: [B, F, D] fp32 on the GPU, or deepctr's list of F pieces [B, 1, D]) -> [B, P, 1], P = F (F - 1) / 2, as
+    deepctr returns it.  No parameters.  One autograd.Function runs satrans_inner_product_fwd / satrans_inner_product_bwd
+    (csrc/pnn.hip): a workgroup reads a row once and writes all of its products; deepctr's two gathered [B, P, D] tensors are
+    never formed.  Not built - NotImplementedError: reduce_sum=False (the [B, P, D] elementwise products, which PNN never
+    uses), more than PNN_MAX_FIELDS fields, D beyond PNN_MAX_DIM."""
+
+    def __init__(self, reduce_sum=True, device='cpu'):
+        super().__init__()
+        if not reduce_sum:
+            raise NotImplementedError("InnerProductLayer: reduce_sum=False is not built (PNN does not use it)")
+        self.reduce_sum = reduce_sum
+
+    def forward(self, inputs):
+        return _InnerProductFn.apply(_pieces(inputs, "InnerProductLayer")).unsqueeze(2)
+
+
+def _outer_desc(x, kind, kernel):
+    d = N.OuterProductDesc()
+    d.B, d.F, d.D, d.kernel_type = x.shape[0], x.shape[1], x.shape[2], kind
+    d.e, d.kernel = x.data_ptr(), kernel.data_ptr()
+    return d
+
+
+class _OuterProductFn(torch.autograd.Function):
+    """out [B, P] of the outer product layer (csrc/pnn.hip); `kernel` in deepctr's shape of its type."""
+
+    @staticmethod
+    def forward(ctx, x, kind, kernel):
+        x, kernel = x.contiguous(), kernel.contiguous()
+        F = x.shape[1]
+        out = torch.empty(x.shape[0], F * (F - 1) // 2, dtype=torch.float32, device=x.device)
+        N.check(N.lib().satrans_outer_product_fwd(C.byref(_outer_desc(x, kind, kernel)), out.data_ptr(), N.stream_handle(x.device)),
+                "satrans_outer_product_fwd")
+        ctx.kind = kind
+        ctx.save_for_backward(x, kernel)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        lib = N.lib()
+        x, kernel = ctx.saved_tensors
+        d = _outer_desc(x, ctx.kind, kernel)
+        work = torch.empty(_native_size(lib.satrans_outer_product_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx, dk = torch.empty_like(x), torch.empty_like(kernel)
+        N.check(lib.satrans_outer_product_bwd(C.byref(d), dout.contiguous().data_ptr(), dx.data_ptr(), work.data_ptr(), dk.data_ptr(),
+                                              N.stream_handle(x.device)), "satrans_outer_product_bwd")
+        return dx, None, dk
+
+
+def _outer_kernel(field_size, embedding_size, kernel_type):
+    """deepctr's `kernel` parameter of a type, xavier-uniform as deepctr initialises it."""
+    n_pairs = field_size * (field_size - 1) // 2
+    shape = {"mat": (embedding_size, n_pairs, embedding_size), "vec": (n_pairs, embedding_size), "num": (n_pairs, 1)}[kernel_type]
+    kernel = nn.Parameter(torch.empty(*shape))
+    nn.init.xavier_uniform_(kernel)
+    return kernel
+
+
+class OutterProductLayer(nn.Module):
+    """deepctr-torch's outer product layer under the reference's spelling, which its PNN calls (models/pnn.py:65,98-99), with
+    deepctr's constructor (`seed` and `device` are accepted and unused).  With K_p = kernel[:, p, :]:
+
+        'mat'   out[b, p] = x_j^T K_p x_i                       kernel [D, P, D]
+        'vec'   out[b, p] = sum_d x_i[d] x_j[d] kernel[p, d]    kernel [P, D]
+        'num'   out[b, p] = kernel[p, 0] sum_d x_i[d] x_j[d]    kernel [P, 1]
+
+    forward(inputs: [B, field_size, embedding_size] fp32 on the GPU, or deepctr's list of pieces [B, 1, D]) -> [B, P].  One
+    autograd.Function runs satrans_outer_product_fwd / satrans_outer_product_bwd (csrc/pnn.hip): 'mat' is one D x D product per
+    pair on the exact f32-input MFMA with the kernel read in place, reduced to one float per row and pair inside the workgroup;
+    deepctr's [B, D, P, D] product is never formed.  `kernel` has deepctr's shape and its xavier-uniform initial bits under a
+    seed.  Another kernel_type raises the reference's ValueError; more than PNN_MAX_FIELDS fields or an embedding size beyond
+    PNN_MAX_DIM NotImplementedError."""
+
+    def __init__(self, field_size, embedding_size, kernel_type='mat', seed=1024, device='cpu'):
+        super().__init__()
+        if kernel_type not in N.PNN_KERNEL_TYPES:
+            raise ValueError("kernel_type must be mat,vec or num")
+        field_size, embedding_size = int(field_size), int(embedding_size)
+        if field_size < 2 or embedding_size < 1:
+            raise ValueError("OutterProductLayer: field_size must be at least 2 and embedding_size positive")
+        if field_size > N.PNN_MAX_FIELDS:
+            raise NotImplementedError(f"OutterProductLayer: up to PNN_MAX_FIELDS = {N.PNN_MAX_FIELDS} fields, got {field_size}")
+        if embedding_size > N.PNN_MAX_DIM:
+            raise NotImplementedError(f"OutterProductLayer: embedding_size up to PNN_MAX_DIM = {N.PNN_MAX_DIM}, got {embedding_size}")
+        self.kernel_type, self.seed = kernel_type, seed
+        self.field_size, self.embedding_size = field_size, embedding_size
+        self.kernel = _outer_kernel(field_size, embedding_size, kernel_type)
+
+    def forward(self, inputs):
+        x = _pieces(inputs, "OutterProductLayer")
+        if x.shape[1] != self.field_size or x.shape[2] != self.embedding_size:
+            raise ValueError(f"OutterProductLayer: expected inputs [B, {self.field_size}, {self.embedding_size}], got {tuple(x.shape)}")
+        if self.kernel.dtype != torch.float32:
+            raise TypeError("OutterProductLayer: inputs, parameters and gradients are float32")
+        return _OuterProductFn.apply(x, N.PNN_KERNEL_TYPES[self.kernel_type], self.kernel)
+
+
+def _pnn_fill(tgt, n_dnn, kernel, dnn, dnn_linear_w, out_bias):
+    """Set the parameter pointers of a satrans_pnn_desc / satrans_pnn_grads; `dnn`: the weights, then the biases."""
+    tgt.kernel = None if kernel is None else kernel.data_ptr()
+    for l in range(n_dnn):
+        tgt.dnn_w[l], tgt.dnn_b[l] = dnn[l].data_ptr(), dnn[n_dnn + l].data_ptr()
+    tgt.dnn_linear_w, tgt.out_bias = dnn_linear_w.data_ptr(), out_bias.data_ptr()
+    return tgt
+
+
+def _pnn_desc(emb, dense, cfg, kernel, dnn, dnn_linear_w, out_bias):
+    n_dnn = len(dnn) // 2
+    d = _pnn_fill(N.PNNDesc(), n_dnn, kernel, dnn, dnn_linear_w, out_bias)
+    d.B, d.F, d.D = emb.shape
+    d.use_inner, d.use_outer, d.kernel_type = cfg
+    d.dense_dim, d.n_dnn = 0 if dense is None else dense.shape[1], n_dnn
+    for l in range(n_dnn):
+        d.width[l] = dnn[l].shape[0]
+    d.emb, d.dense = emb.data_ptr(), None if dense is None else dense.data_ptr()
+    return d
+
+
+class _PNNFn(torch.autograd.Function):
+    """logit [B, 1] of the PNN head (csrc/pnn.hip).  cfg = (use_inner, use_outer, kernel type); `tensors`: the outer product's
+    kernel (with use_outer), the DNN's weights, its biases, dnn_linear's weight, out.bias.  `saved` = the DNN input, the DNN's
+    hidden rows."""
+
+    @staticmethod
+    def forward(ctx, emb, dense, cfg, *tensors):
+        lib = N.lib()
+        dev = emb.device
+        emb = emb.contiguous()
+        dense = None if dense is None else dense.contiguous()
+        tensors = tuple(t.contiguous() for t in tensors)
+        kernel = tensors[0] if cfg[1] else None
+        dnn, dnn_linear_w, out_bias = tensors[(1 if cfg[1] else 0):-2], tensors[-2], tensors[-1]
+        d = _pnn_desc(emb, dense, cfg, kernel, dnn, dnn_linear_w, out_bias)
+        saved = torch.empty(_native_size(lib.satrans_pnn_saved_floats, d), dtype=torch.float32, device=dev)
+        logit = torch.empty(emb.shape[0], 1, dtype=torch.float32, device=dev)
+        N.check(lib.satrans_pnn_fwd(C.byref(d), logit.data_ptr(), saved.data_ptr(), N.stream_handle(dev)), "satrans_pnn_fwd")
+        ctx.cfg, ctx.has_dense = cfg, dense is not None
+        ctx.save_for_backward(emb, saved, *tensors, *(() if dense is None else (dense,)))
+        ctx.mark_non_differentiable(saved)
+        return logit, saved
+
+    @staticmethod
+    def backward(ctx, dlogit, _dsaved):
+        lib = N.lib()
+        emb, saved, *rest = ctx.saved_tensors
+        dense = rest.pop() if ctx.has_dense else None
+        kernel = rest[0] if ctx.cfg[1] else None
+        dnn, dnn_linear_w, out_bias = tuple(rest[(1 if ctx.cfg[1] else 0):-2]), rest[-2], rest[-1]
+        d = _pnn_desc(emb, dense, ctx.cfg, kernel, dnn, dnn_linear_w, out_bias)
+        work = torch.empty(_native_size(lib.satrans_pnn_workspace_floats, d), dtype=torch.float32, device=emb.device)
+        demb = torch.empty_like(emb)
+        ddense = None if dense is None else torch.empty_like(dense)
+        grads = [torch.empty_like(t) for t in rest]
+        g = _pnn_fill(N.PNNGrads(), len(dnn) // 2, grads[0] if ctx.cfg[1] else None, grads[(1 if ctx.cfg[1] else 0):-2], grads[-2],
+                      grads[-1])
+        N.check(lib.satrans_pnn_bwd(C.byref(d), dlogit.contiguous().data_ptr(), demb.data_ptr(),
+                                    None if ddense is None else ddense.data_ptr(), saved.data_ptr(), work.data_ptr(), C.byref(g),
+                                    N.stream_handle(emb.device)), "satrans_pnn_bwd")
+        return (demb, ddense, None, *grads)
+
+
+class PNNHead(nn.Module):
+    """The half of the reference's PNN.forward behind the embedding lookup (models/pnn.py:91-114):
+
+        dnn_input = cat(flatten(emb), inner products (use_inner), outer products (use_outter), dense)
+        logit = dnn_linear(dnn(dnn_input)) + out.bias
+
+    forward(emb [B, field_size, embedding_size] fp32, dense [B, dense_dim] or None) -> logit [B,1]; the caller applies the
+    sigmoid.  PNN has no linear model (pnn.py:43 passes no linear feature columns), so there is no linear_logit.  `emb` is the
+    concatenation of the looked-up embeddings of ALL sparse fields in field order, the domain column included; the reference's
+    `metatrans` flag (pnn.py:85-88) transforms that block first:
+
+        head = PNNHead(F, D, dense_dim, ...); meta = MetaTransformation(D, num_domains)
+        logit = head(meta(domain_ids, emb), dense)
+
+    The whole head is ONE autograd.Function over satrans_pnn_fwd / satrans_pnn_bwd (csrc/pnn.hip): the products written
+    straight into the DNN input (the 'mat' outer product one D x D product per pair on the matrix pipe, reduced inside the
+    workgroup), the embedding gradient written once by one owner per element, and the DNN on the dense layer launcher of
+    csrc/head_layers.h.  With neither product the head is the DNN over cat(flatten(emb), dense).  Empty dnn_hidden_units puts
+    dnn_linear directly on the DNN input (the reference's constructor fails there).
+
+    Parameter names, shapes, state_dict order and initialisation are the reference PNN's: out.bias (zeros),
+    outterproduct.kernel (with use_outter; xavier-uniform), dnn.linears.{l}.{weight,bias} (weights N(0, init_std)),
+    dnn_linear.weight - those entries of a reference checkpoint load with load_state_dict.
+    regularization_loss() -> [1] is what PNN.__init__ itself adds to the reference's regularization_weight (pnn.py:74-76):
+    l2_reg_dnn times the sum of squares of the DNN's weights (not biases) and of dnn_linear.weight, in
+    get_regularization_loss's arithmetic.
+    Not built: a PNN model class behind BaseModel; dropout and activations other than relu in the DNN (NotImplementedError);
+    bf16; more than MMOE_MAX_HIDDEN hidden layers, PNN_MAX_FIELDS fields, an embedding size beyond PNN_MAX_DIM
+    (NotImplementedError at construction)."""
+
+    def __init__(self, field_size, embedding_size, dense_dim=0, dnn_hidden_units=(128, 128), use_inner=True, use_outter=False,
+                 kernel_type='mat', l2_reg_dnn=0, init_std=0.0001, dnn_dropout=0, dnn_activation='relu'):
+        super().__init__()
+        if kernel_type not in N.PNN_KERNEL_TYPES:
+            raise ValueError("kernel_type must be mat,vec or num")
+        if field_size < 2:
+            raise ValueError("PNNHead: field_size must be at least 2 (one pair)")
+        if embedding_size < 1 or dense_dim < 0:
+            raise ValueError("PNNHead: embedding_size must be positive, dense_dim non-negative")
+        if dnn_dropout != 0 or dnn_activation != 'relu':
+            raise NotImplementedError("PNNHead: dropout, batch-norm and activations other than relu are not built")
+        units = [int(u) for u in dnn_hidden_units]
+        if len(units) > N.MMOE_MAX_HIDDEN:
+            raise NotImplementedError(f"PNNHead: up to MMOE_MAX_HIDDEN = {N.MMOE_MAX_HIDDEN} hidden layers, got {len(units)}")
+        if field_size > N.PNN_MAX_FIELDS:
+            raise NotImplementedError(f"PNNHead: up to PNN_MAX_FIELDS = {N.PNN_MAX_FIELDS} fields, got {field_size}")
+        if embedding_size > N.PNN_MAX_DIM:
+            raise NotImplementedError(f"PNNHead: embedding_size up to PNN_MAX_DIM = {N.PNN_MAX_DIM}, got {embedding_size}")
+        self.field_size, self.embedding_size, self.dense_dim = int(field_size), int(embedding_size), int(dense_dim)
+        self.use_inner, self.use_outter, self.kernel_type = bool(use_inner), bool(use_outter), kernel_type
+        self.l2_reg_dnn = float(l2_reg_dnn)
+        n_pairs = self.field_size * (self.field_size - 1) // 2
+        n = self.field_size * self.embedding_size + n_pairs * (int(self.use_inner) + int(self.use_outter)) + self.dense_dim
+        # (first: in the reference's state_dict `out.*` precedes PNN's own modules, because its BaseModel registers that name)
+        self.out = _OutBias()
+        if self.use_inner:
+            self.innerproduct = InnerProductLayer()
+        if self.use_outter:
+            self.outterproduct = OutterProductLayer(self.field_size, self.embedding_size, kernel_type)
+        self.dnn = _TowerDNN(n, units, init_std)
+        self.dnn_linear = nn.Linear(units[-1] if units else n, 1, bias=False)
+
+    def regularization_loss(self):
+        total = torch.zeros((1,), device=self.dnn_linear.weight.device)
+        if self.l2_reg_dnn > 0:
+            for p in [lin.weight for lin in self.dnn.linears] + [self.dnn_linear.weight]:
+                total = total + torch.sum(self.l2_reg_dnn * torch.square(p))
+        return total
+
+    def forward(self, emb, dense=None):
+        if emb.dim() != 3 or emb.shape[1] != self.field_size or emb.shape[2] != self.embedding_size:
+            raise ValueError(f"PNNHead: expected emb [B, {self.field_size}, {self.embedding_size}], got {tuple(emb.shape)}")
+        got = 0 if dense is None else (dense.shape[1] if dense.dim() == 2 else -1)
+        if got != self.dense_dim:
+            raise ValueError(f"PNNHead: expected dense [B, {self.dense_dim}], got {None if dense is None else tuple(dense.shape)}")
+        N.require_gpu(emb, "PNNHead")
+        if emb.dtype != torch.float32 or self.dnn_linear.weight.dtype != torch.float32:
+            raise TypeError("PNNHead: rows, parameters and gradients are float32")
+        tensors = (([self.outterproduct.kernel] if self.use_outter else []) + [lin.weight for lin in self.dnn.linears] +
+                   [lin.bias for lin in self.dnn.linears] + [self.dnn_linear.weight, self.out.bias])
+        cfg = (int(self.use_inner), int(self.use_outter), N.PNN_KERNEL_TYPES[self.kernel_type])
+        logit, _ = _PNNFn.apply(emb, dense if self.dense_dim else None, cfg, *tensors)
+        return logit

@@ -265,6 +265,40 @@ class FiBiNETGrads(C.Structure):
     _fields_ = list(_FIBINET_POINTER_FIELDS)
 
 
+PNN_MAX_FIELDS = 64              # SATRANS_PNN_MAX_FIELDS
+PNN_MAX_DIM = 128                # SATRANS_PNN_MAX_DIM: the embedding size
+PNN_DW_ROW_CHUNK = 256           # SATRANS_PNN_DW_ROW_CHUNK: rows that one partial of the outer product's kernel gradient sums
+PNN_KERNEL_MAT, PNN_KERNEL_VEC, PNN_KERNEL_NUM = 0, 1, 2      # SATRANS_PNN_KERNEL_*
+PNN_KERNEL_TYPES = {"mat": PNN_KERNEL_MAT, "vec": PNN_KERNEL_VEC, "num": PNN_KERNEL_NUM}
+
+
+class InnerProductDesc(C.Structure):
+    """Mirror of `satrans_inner_product_desc`."""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("reserved", C.c_int32), ("e", _vp)]
+
+
+class OuterProductDesc(C.Structure):
+    """Mirror of `satrans_outer_product_desc`."""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("kernel_type", C.c_int32), ("e", _vp), ("kernel", _vp)]
+
+
+# the parameter pointers of satrans_pnn_desc / satrans_pnn_grads in the header's order: (name, per hidden layer)
+PNN_POINTERS = (("kernel", False), ("dnn_w", True), ("dnn_b", True), ("dnn_linear_w", False), ("out_bias", False))
+_PNN_POINTER_FIELDS = [(name, _vp * MMOE_MAX_HIDDEN if per_layer else _vp) for name, per_layer in PNN_POINTERS]
+
+
+class PNNDesc(C.Structure):
+    """Mirror of `satrans_pnn_desc` (the DNN's layer limit is the MMoE head's: MMOE_MAX_HIDDEN)."""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("use_inner", C.c_int32), ("use_outer", C.c_int32),
+                ("kernel_type", C.c_int32), ("dense_dim", C.c_int32), ("n_dnn", C.c_int32), ("width", C.c_int32 * MMOE_MAX_HIDDEN),
+                ("reserved", C.c_int32), ("emb", _vp), ("dense", _vp)] + _PNN_POINTER_FIELDS
+
+
+class PNNGrads(C.Structure):
+    """Mirror of `satrans_pnn_grads`."""
+    _fields_ = list(_PNN_POINTER_FIELDS)
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -396,6 +430,15 @@ SIGNATURES = {
     "satrans_fibinet_workspace_floats": (C.c_int64, [C.POINTER(FiBiNETDesc)]),
     "satrans_fibinet_fwd": (C.c_int, [C.POINTER(FiBiNETDesc), _vp, _vp, _vp]),
     "satrans_fibinet_bwd": (C.c_int, [C.POINTER(FiBiNETDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(FiBiNETGrads), _vp]),
+    "satrans_inner_product_fwd": (C.c_int, [C.POINTER(InnerProductDesc), _vp, _vp]),
+    "satrans_inner_product_bwd": (C.c_int, [C.POINTER(InnerProductDesc), _vp, _vp, _vp]),
+    "satrans_outer_product_workspace_floats": (C.c_int64, [C.POINTER(OuterProductDesc)]),
+    "satrans_outer_product_fwd": (C.c_int, [C.POINTER(OuterProductDesc), _vp, _vp]),
+    "satrans_outer_product_bwd": (C.c_int, [C.POINTER(OuterProductDesc), _vp, _vp, _vp, _vp, _vp]),
+    "satrans_pnn_saved_floats": (C.c_int64, [C.POINTER(PNNDesc)]),
+    "satrans_pnn_workspace_floats": (C.c_int64, [C.POINTER(PNNDesc)]),
+    "satrans_pnn_fwd": (C.c_int, [C.POINTER(PNNDesc), _vp, _vp, _vp]),
+    "satrans_pnn_bwd": (C.c_int, [C.POINTER(PNNDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(PNNGrads), _vp]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
