@@ -8,7 +8,8 @@ import torch
 
 from oracle import satrans_oracle as O
 from tests.helpers import (NATIVE_ADAM_CASES, NATIVE_CASES, NATIVE_TRAIN_CASES, Case, assert_grad_close_but_for_kinks, build_model,
-                           softmax_side_floor)
+                           oracle_grads_probing_kinks, softmax_side_floor)
+from tests.helpers import synthetic_shape_against_oracle as _synthetic_shape_against_oracle
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -32,18 +33,6 @@ def assert_close_but_for_kinks(got, want, rtol, atol, err_msg, frac=5e-4, slack=
     bad = err > tol
     assert float(bad.mean()) <= frac, (err_msg, float(bad.mean()))
     assert bool((err <= slack * tol).all()), (err_msg, float((err / tol).max()))
-
-
-def oracle_grads_probing_kinks(state, X, y, spec, drop=None, eps=2e-6):
-    """O.loss_and_grads plus the number of MetaNet hidden units whose pre-activation the oracle saw within `eps` (relative to the
-    largest pre-activation of its product) of the ReLU's kink: fp32 products of 32 / 64 terms differ by a few 1e-7 of that
-    scale between two evaluation orders, so only such a unit can take one branch in the kernels and the other in the oracle."""
-    O.KINK_PROBE = {"eps": eps, "near_zero": 0}
-    try:
-        out = O.loss_and_grads(state, X, y, spec, drop)
-        return out, int(O.KINK_PROBE["near_zero"])
-    finally:
-        O.KINK_PROBE = None
 
 
 def sd_to_cpu(model):
@@ -2224,69 +2213,6 @@ def test_ragged_batches_gradients_match_the_oracle(name, B):
         # softmax terms) are ~1e-5 and carry ~1e-9 of fp32 cancellation noise in ANY fp32 evaluation: absolute floor 5e-9
         scale = max(1e-6, float(g.abs().max()))
         np.testing.assert_allclose(grads[k].cpu().numpy(), g.numpy(), rtol=0, atol=1e-4 * scale + 5e-9, err_msg=k)
-
-
-def _synthetic_shape_against_oracle(D, H, U, F, generic, B=21, L=2, int_ids=False, ref64=False, grad_tol=2e-4, kink_frac=0.0,
-                                    meta_mode='QK', flag='sota'):
-    from satrans_amd import SATrans, SparseFeat
-    rng = np.random.RandomState(D + F)
-    fields = [f"f{i}" for i in range(F)]
-    vocab = {f: int(rng.randint(5, 60)) for f in fields}
-    vocab[fields[0]] = 4                                   # the scenario column: ids 1..3
-    cols = [SparseFeat(f, vocabulary_size=vocab[f] + 1, embedding_dim=D) for f in fields]
-    torch.manual_seed(3)
-    model = SATrans(cols, cols, [fields[0]], [3], att_layer_num=0, domain_att_layer_num=L, att_head_num=H, use_linear=False,
-                    use_dnn=False, meta_mode=meta_mode, meta_dnn_hidden_units=(U, D), seed='1021', device='cpu', flag=flag)
-    with torch.no_grad():                                  # weights far enough from zero for every gradient to matter
-        for k, p in model.named_parameters():
-            if "embedding" in k:
-                p.mul_(300.0)
-    sd = model.state_dict()
-    state, by_ptr = {}, {}
-    for k, v in sd.items():                                # keep the reference's aliasing (K_meta_mlp is Q_meta_mlp without 'pos')
-        state[k] = by_ptr.setdefault(v.data_ptr(), v.detach().clone())
-    X = np.stack([rng.randint(1 if f == fields[0] else 0, vocab[f], size=B) for f in fields], axis=1).astype(np.float32)
-    y = (rng.rand(B) < 0.4).astype(np.float32)
-    spec = O.PathSpec(sparse=[(f, i) for i, f in enumerate(fields)], dense=[], domain_cols=[0], embedding_dim=D, head_num=H,
-                      layer_num=L, flag=flag, meta_mode=meta_mode, meta_units=[D, U, D])
-    Xt, yt = torch.from_numpy(X), torch.from_numpy(y)
-    Xg = Xt.long() if int_ids else Xt                     # the id matrix as the kernels get it (int64: SATRANS_ID_I64)
-    if ref64:                                             # the oracle in fp64: the difference is then the kernels' rounding alone
-        conv = {}
-        state = {k: conv.setdefault(id(v), v.double()) for k, v in state.items()}
-    model.to(DEV); model.device = DEV
-    model.compile("adam", "binary_crossentropy")
-    for train in (False, True):
-        model.train(train)
-        eng = model._require_engine()
-        bce, reg, grads = eng.loss_and_grads(Xg.to(DEV), yt.to(DEV))
-        assert bool(eng._ws[B]["generic"]) == generic, "unexpected layer path"
-        drop = O.Dropper("masks", 0.1, O.dropout_masks(eng.drop_seed, eng.drop_step, B, F, D, H, L, 0.1)) if train else None
-        (bce_ref, reg_ref, g_ref), kinks = oracle_grads_probing_kinks(state, Xt, yt, spec, drop)
-        if not train:
-            model(Xg.to(DEV))
-            _, logit_ref = O.forward(state, Xt, spec)
-            np.testing.assert_allclose(eng.last_logit().cpu().numpy().reshape(-1), logit_ref.float().numpy().reshape(-1), rtol=0,
-                                       atol=2e-5 * max(1.0, float(logit_ref.abs().max())))
-        assert bce == pytest.approx(bce_ref, rel=1e-5)
-        for k, g in g_ref.items():
-            if k in grads:
-                scale = max(1e-6, float(g.abs().max()))
-                got_g, want_g = grads[k].cpu().numpy().astype(np.float64), g.double().numpy()
-                if kink_frac > 0:
-                    # ReLU kinks: a MetaNet hidden unit whose pre-activation is within rounding of zero takes one branch here and
-                    # the other in the oracle (any two evaluation orders do that to each other); its dh then reaches - or does not
-                    # reach - the rows of ONE token.  With tens of millions of hidden units per step a few such tokens are certain,
-                    # so a small fraction of a tensor's elements is held to 10x the bound only.
-                    err = np.abs(got_g - want_g)
-                    assert float((err > grad_tol * scale + 1e-8).mean()) <= kink_frac, (k, train, float((err > grad_tol * scale + 1e-8).mean()))
-                    assert float(err.max()) <= 10 * grad_tol * scale + 1e-8, (k, train, float(err.max()), scale)
-                    continue
-                if train:
-                    assert_grad_close_but_for_kinks(got_g, want_g, grad_tol * scale + softmax_side_floor(k, g_ref, 1e-8),
-                                                    f"{k} train={train} (oracle: {kinks} hidden units on the kink)", kinks=kinks)
-                else:
-                    np.testing.assert_allclose(got_g, want_g, rtol=0, atol=grad_tol * scale + 1e-8, err_msg=f"{k} train={train}")
 
 
 @pytest.mark.parametrize("D,H,U,F", [(128, 8, 64, 9), (64, 8, 32, 33), (32, 2, 64, 70), (64, 4, 48, 24), (16, 1, 16, 5)])
