@@ -868,10 +868,15 @@ extern "C" int satrans_layer_fwd_bf16_supported(const satrans_layer_desc* d) {
     if (!d || (d->flags & SATRANS_TRAIN)) return 0;
     const bool gate = d->flags & SATRANS_GATE, bilin = d->flags & SATRANS_BILINEAR;
     if (gate && bilin) return 0;
-    if (gate || bilin) return d->D == 32 && d->H == 4;
+    // ... and a tile of one sample has to fit beside the images (launch_fwd_bf16's own limit): with two generated tables ('pos')
+    // (64, 128, 4) holds 48 token rows, not 64 - the launch used to refuse such a shape after this query had accepted it
+    const bool same_tab = d->tab_q == d->tab_k;
+    const int mod = bf16_mod_of(d);
+    if (gate || bilin) return d->D == 32 && d->H == 4 && bf16_fwd_lds_bytes(1, d->F, 32, 64, same_tab, mod) <= 156 * 1024;
     const bool meta = d->flags & (SATRANS_META_Q | SATRANS_META_K);
-    if (d->D == 32 && d->H == 4 && (!meta || d->U == 64)) return 1;
-    if (d->D == 64 && d->H == 4 && (!meta || d->U == 128) && d->F <= 64) return 1;
+    if (d->D == 32 && d->H == 4 && (!meta || d->U == 64)) return bf16_fwd_lds_bytes(1, d->F, 32, 64, same_tab, 0) <= 156 * 1024;
+    if (d->D == 64 && d->H == 4 && (!meta || d->U == 128) && d->F <= 64)
+        return bf16_fwd_lds_bytes(1, d->F, 64, 128, same_tab, 0) <= 156 * 1024;
     return 0;
 }
 

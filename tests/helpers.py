@@ -151,6 +151,66 @@ def oracle_grads_probing_kinks(state, X, y, spec, drop=None, eps=2e-6):
         O.KINK_PROBE = None
 
 
+class SyntheticModel:
+    """A seeded synthetic model through the public API, built on the CPU, and the same parameters as a state_dict-shaped dict
+    for the oracle (aliased keys one tensor): the construction of synthetic_shape_against_oracle - SATrans(..., seed='1021')
+    behind torch.manual_seed(3), embedding parameters x `emb` - with three additions.  Every LayerNorm vector is redrawn
+    (weight 1 + 0.2 n, bias 0.1 n: at their initial 1 / 0 the Q-side and K-side vectors are equal and a kernel that read the
+    wrong one would go unnoticed), the scenario encoder's weight is scaled by `gen`, and `n_dense` DenseFeat columns may follow
+    the sparse ones.  `scen_ids`: the scenario column (ids 1..3; id 0 stays unused); `seed`: of the other id columns;
+    `vocab`: range the fields' vocabulary sizes are drawn from.  Nothing here needs a device;
+    on_device() moves the model there and returns its engine."""
+
+    def __init__(self, D, H, U, F, L=2, flag="sota", meta_mode="QK", scen_ids=None, B=21, n_dense=0, emb=300.0, gen=1.0, seed=0, vocab=(5, 60)):
+        from satrans_amd import SATrans, SparseFeat, DenseFeat
+        rng = np.random.RandomState(D + F)
+        self.fields = [f"f{i}" for i in range(F)]
+        vocab = {f: int(rng.randint(*vocab)) for f in self.fields}
+        vocab[self.fields[0]] = 4                              # the scenario column: ids 1..3
+        self.dense = [f"d{i}" for i in range(n_dense)]
+        cols = [SparseFeat(f, vocabulary_size=vocab[f] + 1, embedding_dim=D) for f in self.fields] + \
+               [DenseFeat(f, 1) for f in self.dense]
+        torch.manual_seed(3)
+        model = SATrans(cols, cols, [self.fields[0]], [3], att_layer_num=0, domain_att_layer_num=L, att_head_num=H,
+                        use_linear=False, use_dnn=False, meta_mode=meta_mode, meta_dnn_hidden_units=(U, D), seed='1021',
+                        device='cpu', flag=flag)
+        gen_ = torch.Generator().manual_seed(7)
+        with torch.no_grad():
+            for k, p in model.named_parameters():
+                if "embedding" in k:
+                    p.mul_(emb)
+                elif k.endswith("layer_norm.weight"):
+                    p.copy_(1.0 + 0.2 * torch.randn(p.shape, generator=gen_))
+                elif k.endswith("layer_norm.bias"):
+                    p.copy_(0.1 * torch.randn(p.shape, generator=gen_))
+                elif k == "domain_map_dnn_Q.linears.0.weight":
+                    p.mul_(gen)
+        by_ptr = {}
+        self.state = {k: by_ptr.setdefault(v.data_ptr(), v.detach().clone()) for k, v in model.state_dict().items()}
+        if scen_ids is not None:
+            B = len(scen_ids)
+        rng = np.random.RandomState(1000 * seed + D + F)       # `seed`: another id matrix for the same model
+        X = np.stack([rng.randint(1 if f == self.fields[0] else 0, vocab[f], size=B) for f in self.fields], axis=1).astype(np.float32)
+        if scen_ids is not None:
+            X[:, 0] = np.asarray(scen_ids, dtype=np.float32)
+        if n_dense:
+            X = np.concatenate([X, rng.rand(B, n_dense).astype(np.float32)], axis=1)
+        self.X = torch.from_numpy(X)
+        self.spec = O.PathSpec(sparse=[(f, i) for i, f in enumerate(self.fields)], dense=[(F + i, F + i + 1) for i in range(n_dense)],
+                               domain_cols=[0], embedding_dim=D, head_num=H, layer_num=L, flag=flag, meta_mode=meta_mode,
+                               meta_units=[D, U, D])
+        self.model, self.eng = model, None
+
+    def on_device(self):
+        model = self.model
+        model.to(DEV)
+        model.device = DEV
+        model.compile("adam", "binary_crossentropy")
+        model.eval()
+        self.eng = model._require_engine()
+        return self.eng
+
+
 def synthetic_shape_against_oracle(D, H, U, F, generic, B=21, L=2, int_ids=False, ref64=False, grad_tol=2e-4, kink_frac=0.0,
                                    meta_mode='QK', flag='sota', scen_ids=None, first_scen_ids=None, check_attention=False,
                                    route_check=None, tag=None):
