@@ -44,7 +44,8 @@ extern "C" {
  *    network (satrans_cin_desc, satrans_cin_grads, satrans_cin_*), and DCN's cross network (satrans_cross_desc,
  *    satrans_cross_grads, satrans_cross_*), and FiBiNET's SENet, bilinear interaction and head (satrans_senet_*,
  *    satrans_bilinear_*, satrans_fibinet_*), and PNN's inner and outer product layers and head (satrans_inner_product_*,
- *    satrans_outer_product_*, satrans_pnn_*). */
+ *    satrans_outer_product_*, satrans_pnn_*), and FM, BiInteractionPooling, AFM and the DeepFM / NFM heads (satrans_fm_*,
+ *    satrans_bipool_*, satrans_afm_*, satrans_fmhead_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -937,6 +938,93 @@ int64_t satrans_pnn_workspace_floats(const satrans_pnn_desc* d);
 int satrans_pnn_fwd(const satrans_pnn_desc* d, float* logit, float* saved, void* stream);
 int satrans_pnn_bwd(const satrans_pnn_desc* d, const float* dlogit, float* demb, float* ddense, const float* saved, float* workspace,
                     const satrans_pnn_grads* g, void* stream);
+
+/* FM, BiInteractionPooling and AFMLayer of deepctr-torch 0.2.9, which the reference's models/deepfm.py, nfm.py and afm.py
+ * import, and the halves of their forward behind the lookup (deepfm.py:87-113, nfm.py:73-83, afm.py:66-73).  With e [B, F, D]
+ * and S = sum_f e_f:
+ *     FM        out[b]   = 0.5 sum_d (S_d^2 - sum_f e_fd^2)                       de_f  = dout (S - e_f)
+ *     bipool    out[b,d] = 0.5 (S_d^2 - sum_f e_fd^2)                             de_fd = dout_d (S_d - e_fd)
+ *     AFM       over the pairs p = (i, j), i < j, in itertools.combinations order (P = F (F - 1) / 2):  x_p = e_i * e_j,
+ *               t_p = relu(x_p attention_W + attention_b), a = softmax_p(t_p projection_h), ao = sum_p a_p x_p,
+ *               out[b] = ao . projection_p (+ linear_logit[b] + out_bias[0], each when not null)
+ *     DEEPFM    logit = linear_logit + FM(e) (use_fm) + dnn_linear(dnn([ flatten(e) | dense ])) (n_dnn > 0) + out_bias
+ *     NFM       logit = linear_logit + dnn_linear(dnn([ bipool(e) | dense ])) + out_bias          (n_dnn > 0 required)
+ * fp32 throughout.  2 to SATRANS_FM_MAX_FIELDS fields, D up to SATRANS_FM_MAX_DIM (any D), A from 1 to SATRANS_AFM_MAX_FACTOR,
+ * up to SATRANS_MMOE_MAX_HIDDEN hidden layers, any positive B whose launches fit the grid; SATRANS_E_UNSUPPORTED beyond, decided
+ * before a device is touched.
+ * satrans_fm_fwd: out [B].  satrans_bipool_fwd: out [B, D].  Their _bwd take dout of that shape and WRITE de [B, F, D].
+ * satrans_afm_fwd: out [B]; saved = a [B, P] (deepctr's normalized_att_score), ao [B, D]: B (P + D) floats.  satrans_afm_bwd
+ * takes dout [B] and WRITES de and every gradient of g (g->out_bias, the sum of dout, may be null when d->out_bias is); its
+ * workspace is one partial of D A + 2 A + D floats per workgroup, at most SATRANS_AFM_MAX_WORKGROUPS of them, merged in
+ * workgroup order.  The gradient of linear_logit is dout itself.
+ * satrans_fmhead_fwd: logit [B, 1]; saved = the DNN input [B, (DEEPFM: F D, NFM: D) + dense_dim], the hidden rows (nothing
+ * without a DNN).  satrans_fmhead_bwd WRITES demb [B, F, D], ddense [B, dense_dim] (null when dense_dim = 0 or without a DNN)
+ * and every gradient of g; the gradient of linear_logit is dlogit itself.
+ * No floating-point atomics: equal inputs give equal bits, and a sample's out / logit and de row are the same bits alone as
+ * inside a batch. */
+#define SATRANS_FM_MAX_FIELDS 64
+#define SATRANS_FM_MAX_DIM 128
+#define SATRANS_AFM_MAX_FACTOR 64
+#define SATRANS_AFM_MAX_WORKGROUPS 1024
+#define SATRANS_FMHEAD_DEEPFM 0
+#define SATRANS_FMHEAD_NFM 1
+typedef struct satrans_fm_desc {
+    int32_t B, F, D, reserved;
+    const float* e;                         /* [B, F, D] */
+} satrans_fm_desc;
+int satrans_fm_fwd(const satrans_fm_desc* d, float* out, void* stream);
+int satrans_fm_bwd(const satrans_fm_desc* d, const float* dout, float* de, void* stream);
+int satrans_bipool_fwd(const satrans_fm_desc* d, float* out, void* stream);
+int satrans_bipool_bwd(const satrans_fm_desc* d, const float* dout, float* de, void* stream);
+typedef struct satrans_afm_desc {
+    int32_t B, F, D, A;
+    const float* e;                         /* [B, F, D] */
+    const float* attention_W;               /* [D, A] */
+    const float* attention_b;               /* [A] */
+    const float* projection_h;              /* [A, 1] */
+    const float* projection_p;              /* [D, 1] */
+    const float* linear_logit;              /* [B, 1], null: none */
+    const float* out_bias;                  /* [1], null: none */
+} satrans_afm_desc;
+typedef struct satrans_afm_grads {
+    float* attention_W;
+    float* attention_b;
+    float* projection_h;
+    float* projection_p;
+    float* out_bias;
+} satrans_afm_grads;
+int64_t satrans_afm_saved_floats(const satrans_afm_desc* d);
+int64_t satrans_afm_workspace_floats(const satrans_afm_desc* d);
+int satrans_afm_fwd(const satrans_afm_desc* d, float* out, float* saved, void* stream);
+int satrans_afm_bwd(const satrans_afm_desc* d, const float* dout, float* de, const float* saved, float* workspace,
+                    const satrans_afm_grads* g, void* stream);
+typedef struct satrans_fmhead_desc {
+    int32_t B, F, D;
+    int32_t kind;                           /* SATRANS_FMHEAD_* */
+    int32_t use_fm;                         /* DEEPFM: the FM term */
+    int32_t dense_dim, n_dnn;
+    int32_t reserved;
+    int32_t width[SATRANS_MMOE_MAX_HIDDEN];
+    int32_t reserved2;
+    const float* emb;                       /* [B, F, D] */
+    const float* dense;                     /* [B, dense_dim], null when dense_dim = 0 */
+    const float* linear_logit;              /* [B, 1], null: none */
+    const float* dnn_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* dnn_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* dnn_linear_w;              /* [1, last width] */
+    const float* out_bias;                  /* [1] */
+} satrans_fmhead_desc;
+typedef struct satrans_fmhead_grads {
+    float* dnn_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* dnn_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* dnn_linear_w;
+    float* out_bias;
+} satrans_fmhead_grads;
+int64_t satrans_fmhead_saved_floats(const satrans_fmhead_desc* d);
+int64_t satrans_fmhead_workspace_floats(const satrans_fmhead_desc* d);
+int satrans_fmhead_fwd(const satrans_fmhead_desc* d, float* logit, float* saved, void* stream);
+int satrans_fmhead_bwd(const satrans_fmhead_desc* d, const float* dlogit, float* demb, float* ddense, const float* saved,
+                       float* workspace, const satrans_fmhead_grads* g, void* stream);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

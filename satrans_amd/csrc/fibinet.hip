@@ -655,6 +655,12 @@ extern "C" int satrans_fibinet_fwd(const satrans_fibinet_desc* d, float* logit, 
                     SATRANS_E_BADARG, "fibinet_fwd: null pointer");
     float* a = saved + Y.sv_a;
     float* x = saved + Y.sv_x;
+    // (the up to three floats between hid and the aligned x belong to nobody: zero, so that equal inputs give an equal buffer)
+    const int64_t pad0 = Y.sv_hid + (int64_t)d->B * d->R;
+    if (Y.sv_x > pad0 && hipMemsetAsync(saved + pad0, 0, (size_t)(Y.sv_x - pad0) * sizeof(float), st) != hipSuccess) {
+        set_error("fibinet_fwd: hipMemsetAsync failed");
+        return SATRANS_E_LAUNCH;
+    }
     if (int rc = se_fwd(Y.s, d->emb, d->se_w1, d->se_w2, a, saved + Y.sv_hid, nullptr, st)) return rc;
     if (int rc = bil_fwd(Y.s, d->emb, d->bilinear_w, a, x, Y.ld, st)) return rc;
     if (Y.dense) {

@@ -43,14 +43,15 @@ inline int64_t layer_part(const Rows& r, bool routed, const Lyr& y, const char* 
     return units * y.N * ((int64_t)y.K + 1);
 }
 
-// out[:, block * ogo + n] = epilogue(in[:, block * igo + k] W^T) of one layer; in / out are rows of ldin / ldout floats
+// out[:, block * ogo + n] = epilogue(in[:, block * igo + k] W^T) of one layer; in / out are rows of ldin / ldout floats; `add`:
+// added to what out holds
 template <bool ROUTED>
 int launch_fwd(const Rows& r, const Lyr& y, const float* in, int ldin, int igo, int relu, float* out, int ldout, int ogo,
-               hipStream_t st) {
+               hipStream_t st, int add = 0) {
     const int ntiles = (int)ceil_div(y.N, kTN);
     const int64_t units = (ROUTED ? r.slots : r.tiles) * y.G;
     mmoe_gemm_kernel<false, ROUTED><<<(unsigned)(units * ntiles), kThreads, 0, st>>>(in, ldin, igo, r.order, r.seg, r.B, y.K, y.N, r.T, y.G,
-                                                                                     ntiles, y.w, y.b, relu, nullptr, 0, out, ldout, ogo);
+                                                                                     ntiles, y.w, y.b, relu, nullptr, add, out, ldout, ogo);
     SATRANS_CHECK_LAUNCH("mmoe_gemm_kernel (forward)");
     return SATRANS_OK;
 }
@@ -142,13 +143,14 @@ inline void set_grads(Chain& c, float* const* w, float* const* b, float* final_w
     }
 }
 
-// a gate or tower DNN and its final layer, forward: hidden rows into saved, the final layer's output into `out`
+// a gate or tower DNN and its final layer, forward: hidden rows into saved, the final layer's output into `out` (`add`: added
+// to what `out` holds)
 template <bool ROUTED>
-int dnn_fwd(const Rows& r, const Chain& c, const float* in, float* saved, float* out, hipStream_t st) {
+int dnn_fwd(const Rows& r, const Chain& c, const float* in, float* saved, float* out, hipStream_t st, int add = 0) {
     for (int l = 0; l < c.n; ++l) {
         const bool fin = l == c.n - 1;
         float* o = fin ? out : saved + c.s[l];
-        if (int rc = launch_fwd<ROUTED>(r, c.y[l], in, c.y[l].K, 0, fin ? 0 : 1, o, c.y[l].N, 0, st)) return rc;
+        if (int rc = launch_fwd<ROUTED>(r, c.y[l], in, c.y[l].K, 0, fin ? 0 : 1, o, c.y[l].N, 0, st, fin ? add : 0)) return rc;
         in = o;
     }
     return SATRANS_OK;

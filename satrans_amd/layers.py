@@ -45,8 +45,14 @@
     D x D product per pair on the matrix pipe reduced inside the workgroup; and `PNNHead`, the part of PNN.forward behind the
     embeddings (pnn.py:91-114), the whole head one autograd.Function (csrc/pnn.hip).
 
+  * `FM`, `BiInteractionPooling` and `AFMLayer` - deepctr's pairwise-interaction layers, which the reference's DeepFM, NFM and AFM
+    call (models/deepfm.py:57, nfm.py:56, afm.py:47): FM and the pooling one pass over the rows each way; AFM with a sample's rows
+    staged once, the pair products, the scores, the softmax and the relu mask kept on chip - none of deepctr's [B, P, D] tensors
+    exists; and `DeepFMHead`, `NFMHead` and `AFMHead`, the parts of the three forwards behind the embeddings (deepfm.py:87-113,
+    nfm.py:73-83, afm.py:66-73) with linear_logit and out.bias, each head one autograd.Function (csrc/fm.hip).
+
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
-csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip, csrc/fibinet.hip, csrc/pnn.hip) wrapped
+csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip, csrc/fibinet.hip, csrc/pnn.hip, csrc/fm.hip) wrapped
 in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
@@ -1887,17 +1893,18 @@ class FiBiNETHead(nn.Module):
         return logit if linear_logit is None else linear_logit + logit
 
 
-def _pieces(inputs, what):
-    """[B, F, D] of deepctr's list of [B, 1, D] pieces (or of a [B, F, D] tensor as it is)."""
+def _pieces(inputs, what, family="PNN"):
+    """[B, F, D] of deepctr's list of [B, 1, D] pieces (or of a [B, F, D] tensor as it is); `family`: whose limits apply."""
     x = torch.cat(list(inputs), dim=1) if isinstance(inputs, (list, tuple)) else inputs
     if x.dim() != 3 or x.shape[1] < 2:
         raise ValueError(f"{what}: expected [B, F, D] with F >= 2 or a list of [B, 1, D] pieces, got {tuple(x.shape)}")
     N.require_gpu(x, what)
     if x.dtype != torch.float32:
         raise TypeError(f"{what}: inputs, parameters and gradients are float32")
-    if x.shape[1] > N.PNN_MAX_FIELDS or x.shape[2] > N.PNN_MAX_DIM:
-        raise NotImplementedError(f"{what}: up to PNN_MAX_FIELDS = {N.PNN_MAX_FIELDS} fields and D up to PNN_MAX_DIM = "
-                                  f"{N.PNN_MAX_DIM}, got {tuple(x.shape)}")
+    max_fields, max_dim = getattr(N, f"{family}_MAX_FIELDS"), getattr(N, f"{family}_MAX_DIM")
+    if x.shape[1] > max_fields or x.shape[2] > max_dim:
+        raise NotImplementedError(f"{what}: up to {family}_MAX_FIELDS = {max_fields} fields and D up to {family}_MAX_DIM = "
+                                  f"{max_dim}, got {tuple(x.shape)}")
     return x
 
 
@@ -2179,3 +2186,398 @@ class PNNHead(nn.Module):
         cfg = (int(self.use_inner), int(self.use_outter), N.PNN_KERNEL_TYPES[self.kernel_type])
         logit, _ = _PNNFn.apply(emb, dense if self.dense_dim else None, cfg, *tensors)
         return logit
+
+
+def _fm_desc(x):
+    d = N.FMDesc()
+    d.B, d.F, d.D, d.e = x.shape[0], x.shape[1], x.shape[2], x.data_ptr()
+    return d
+
+
+class _FMFn(torch.autograd.Function):
+    """FM (pooled = False): out [B, 1]; BiInteractionPooling (pooled = True): out [B, 1, D] (csrc/fm.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, pooled):
+        x = x.contiguous()
+        lib = N.lib()
+        out = torch.empty((x.shape[0], 1, x.shape[2]) if pooled else (x.shape[0], 1), dtype=torch.float32, device=x.device)
+        fn, name = (lib.satrans_bipool_fwd, "satrans_bipool_fwd") if pooled else (lib.satrans_fm_fwd, "satrans_fm_fwd")
+        N.check(fn(C.byref(_fm_desc(x)), out.data_ptr(), N.stream_handle(x.device)), name)
+        ctx.pooled = pooled
+        ctx.save_for_backward(x)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, = ctx.saved_tensors
+        lib = N.lib()
+        dx = torch.empty_like(x)
+        fn, name = (lib.satrans_bipool_bwd, "satrans_bipool_bwd") if ctx.pooled else (lib.satrans_fm_bwd, "satrans_fm_bwd")
+        N.check(fn(C.byref(_fm_desc(x)), dout.contiguous().data_ptr(), dx.data_ptr(), N.stream_handle(x.device)), name)
+        return dx, None
+
+
+class FM(nn.Module):
+    """deepctr-torch's factorization machine layer, which the reference's DeepFM and AFM call (models/deepfm.py:57,98,
+    afm.py:51,71): the pairwise interactions without a linear term or a bias,
+
+        out[b, 0] = 0.5 sum_d ((sum_f x_f[d])^2 - sum_f x_f[d]^2)
+
+    forward(inputs: [B, F, D] fp32 on the GPU, or deepctr's list of F pieces [B, 1, D]) -> [B, 1].  No parameters.  One
+    autograd.Function over satrans_fm_fwd / satrans_fm_bwd (csrc/fm.hip): one pass over the rows each way.  More than
+    FM_MAX_FIELDS fields or D beyond FM_MAX_DIM: NotImplementedError."""
+
+    def forward(self, inputs):
+        return _FMFn.apply(_pieces(inputs, "FM", "FM"), False)
+
+
+class BiInteractionPooling(nn.Module):
+    """deepctr-torch's bi-interaction pooling, which the reference's NFM calls (models/nfm.py:56,75): FM's cross term before
+    the sum over the embedding,
+
+        out[b, 0, d] = 0.5 ((sum_f x_f[d])^2 - sum_f x_f[d]^2)
+
+    forward(inputs: [B, F, D] fp32 on the GPU, or deepctr's list of pieces) -> [B, 1, D].  No parameters.  One autograd.Function
+    over satrans_bipool_fwd / satrans_bipool_bwd (csrc/fm.hip).  Limits as FM's."""
+
+    def forward(self, inputs):
+        return _FMFn.apply(_pieces(inputs, "BiInteractionPooling", "FM"), True)
+
+
+def _afm_fill(tgt, params, out_bias):
+    for name, t in zip(N.AFM_POINTERS, params):
+        setattr(tgt, name, t.data_ptr())
+    tgt.out_bias = None if out_bias is None else out_bias.data_ptr()
+    return tgt
+
+
+def _afm_desc(x, params, linear_logit, out_bias):
+    d = _afm_fill(N.AFMDesc(), params, out_bias)
+    d.B, d.F, d.D = x.shape
+    d.A = params[0].shape[1]
+    d.e = x.data_ptr()
+    d.linear_logit = None if linear_logit is None else linear_logit.data_ptr()
+    return d
+
+
+class _AFMFn(torch.autograd.Function):
+    """out [B, 1] of AFMLayer, plus linear_logit and out.bias (each or None) in the same launch (csrc/fm.hip).  `saved` = the
+    normalised attention scores [B, P], the attention output [B, D]."""
+
+    @staticmethod
+    def forward(ctx, x, linear_logit, out_bias, *params):
+        lib = N.lib()
+        x = x.contiguous()
+        params = tuple(p.contiguous() for p in params)
+        linear_logit = None if linear_logit is None else linear_logit.contiguous()
+        d = _afm_desc(x, params, linear_logit, out_bias)
+        saved = torch.empty(_native_size(lib.satrans_afm_saved_floats, d), dtype=torch.float32, device=x.device)
+        out = torch.empty(x.shape[0], 1, dtype=torch.float32, device=x.device)
+        N.check(lib.satrans_afm_fwd(C.byref(d), out.data_ptr(), saved.data_ptr(), N.stream_handle(x.device)), "satrans_afm_fwd")
+        ctx.has_lin, ctx.has_bias = linear_logit is not None, out_bias is not None
+        ctx.save_for_backward(x, saved, *params, *(() if out_bias is None else (out_bias,)))
+        ctx.mark_non_differentiable(saved)
+        return out, saved
+
+    @staticmethod
+    def backward(ctx, dout, _dsaved):
+        lib = N.lib()
+        x, saved, *params = ctx.saved_tensors
+        out_bias = params.pop() if ctx.has_bias else None
+        dout = dout.contiguous()
+        d = _afm_desc(x, params, None, out_bias)
+        work = torch.empty(_native_size(lib.satrans_afm_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        grads = [torch.empty_like(p) for p in params]
+        dbias = None if out_bias is None else torch.empty_like(out_bias)
+        g = _afm_fill(N.AFMGrads(), grads, dbias)
+        N.check(lib.satrans_afm_bwd(C.byref(d), dout.data_ptr(), dx.data_ptr(), saved.data_ptr(), work.data_ptr(), C.byref(g),
+                                    N.stream_handle(x.device)), "satrans_afm_bwd")
+        return (dx, dout if ctx.has_lin else None, dbias, *grads)
+
+
+class AFMLayer(nn.Module):
+    """deepctr-torch's attentional factorization machine layer, which the reference's AFM calls (models/afm.py:47,69), with
+    deepctr's constructor (`l2_reg_w`, `seed` and `device` are accepted and unused: the reference regularises attention_W through
+    the model).  Over the pairs p = (i, j), i < j, in itertools.combinations order:
+
+        x_p = x_i * x_j                                   a = softmax_p(relu(x_p attention_W + attention_b) projection_h)
+        out = (sum_p a_p x_p) projection_p
+
+    forward(inputs: deepctr's list of F pieces [B, 1, D], or [B, F, D], fp32 on the GPU) -> [B, 1].  Afterwards
+    `normalized_att_score` [B, P, 1] holds the attention scores (detached), as deepctr's attribute does: it is the buffer the
+    backward reads.  Parameters in deepctr's creation order: attention_W [D, A], attention_b [A] (zeros), projection_h [A, 1],
+    projection_p [D, 1], the three matrices xavier-normal drawn in deepctr's order, so the initial bits under a seed are
+    deepctr's.  One autograd.Function over satrans_afm_fwd / satrans_afm_bwd (csrc/fm.hip): a workgroup stages a sample's rows
+    once and forms the pair products on chip; none of deepctr's [B, P, D] tensors exists, and the backward recomputes the
+    products and the relu mask.  Not built - NotImplementedError: dropout_rate != 0; an attention factor beyond AFM_MAX_FACTOR;
+    more than FM_MAX_FIELDS fields; an embedding size beyond FM_MAX_DIM."""
+
+    def __init__(self, in_features, attention_factor=4, l2_reg_w=0, dropout_rate=0, seed=1024, device='cpu'):
+        super().__init__()
+        if dropout_rate != 0:
+            raise NotImplementedError("AFMLayer: dropout is not built")
+        in_features, attention_factor = int(in_features), int(attention_factor)
+        if in_features < 1 or attention_factor < 1:
+            raise ValueError("AFMLayer: in_features and attention_factor must be positive")
+        if in_features > N.FM_MAX_DIM:
+            raise NotImplementedError(f"AFMLayer: in_features up to FM_MAX_DIM = {N.FM_MAX_DIM}, got {in_features}")
+        if attention_factor > N.AFM_MAX_FACTOR:
+            raise NotImplementedError(f"AFMLayer: attention_factor up to AFM_MAX_FACTOR = {N.AFM_MAX_FACTOR}, got {attention_factor}")
+        self.attention_factor, self.l2_reg_w, self.dropout_rate, self.seed = attention_factor, l2_reg_w, dropout_rate, seed
+        self.attention_W = nn.Parameter(torch.empty(in_features, attention_factor))
+        self.attention_b = nn.Parameter(torch.empty(attention_factor))
+        self.projection_h = nn.Parameter(torch.empty(attention_factor, 1))
+        self.projection_p = nn.Parameter(torch.empty(in_features, 1))
+        for tensor in (self.attention_W, self.projection_h, self.projection_p):
+            nn.init.xavier_normal_(tensor)
+        nn.init.zeros_(self.attention_b)
+        self.normalized_att_score = None
+
+    def _run(self, inputs, linear_logit, out_bias, what):
+        x = _pieces(inputs, what, "FM")
+        if x.shape[2] != self.attention_W.shape[0]:
+            raise ValueError(f"{what}: expected an embedding size of {self.attention_W.shape[0]}, got {tuple(x.shape)}")
+        if self.attention_W.dtype != torch.float32:
+            raise TypeError(f"{what}: inputs, parameters and gradients are float32")
+        out, saved = _AFMFn.apply(x, linear_logit, out_bias, self.attention_W, self.attention_b, self.projection_h, self.projection_p)
+        n_pairs = x.shape[1] * (x.shape[1] - 1) // 2
+        self.normalized_att_score = saved[:x.shape[0] * n_pairs].view(x.shape[0], n_pairs, 1)
+        return out
+
+    def forward(self, inputs):
+        return self._run(inputs, None, None, "AFMLayer")
+
+
+def _fmhead_fill(tgt, n_dnn, dnn, dnn_linear_w, out_bias):
+    """Set the parameter pointers of a satrans_fmhead_desc / satrans_fmhead_grads; `dnn`: the weights, then the biases."""
+    for l in range(n_dnn):
+        tgt.dnn_w[l], tgt.dnn_b[l] = dnn[l].data_ptr(), dnn[n_dnn + l].data_ptr()
+    tgt.dnn_linear_w = None if dnn_linear_w is None else dnn_linear_w.data_ptr()
+    tgt.out_bias = out_bias.data_ptr()
+    return tgt
+
+
+def _fmhead_desc(emb, dense, linear_logit, cfg, dnn, dnn_linear_w, out_bias):
+    n_dnn = len(dnn) // 2
+    d = _fmhead_fill(N.FMHeadDesc(), n_dnn, dnn, dnn_linear_w, out_bias)
+    d.B, d.F, d.D = emb.shape
+    d.kind, d.use_fm = cfg
+    d.dense_dim, d.n_dnn = 0 if dense is None else dense.shape[1], n_dnn
+    for l in range(n_dnn):
+        d.width[l] = dnn[l].shape[0]
+    d.emb, d.dense = emb.data_ptr(), None if dense is None else dense.data_ptr()
+    d.linear_logit = None if linear_logit is None else linear_logit.data_ptr()
+    return d
+
+
+class _FMHeadFn(torch.autograd.Function):
+    """logit [B, 1] of the DeepFM and NFM heads (csrc/fm.hip).  cfg = (kind, use_fm); `tensors`: the DNN's weights, its biases,
+    dnn_linear's weight (those with a DNN), out.bias.  `saved` = the DNN input, the DNN's hidden rows."""
+
+    @staticmethod
+    def forward(ctx, emb, dense, linear_logit, cfg, *tensors):
+        lib = N.lib()
+        dev = emb.device
+        emb = emb.contiguous()
+        dense = None if dense is None else dense.contiguous()
+        linear_logit = None if linear_logit is None else linear_logit.contiguous()
+        tensors = tuple(t.contiguous() for t in tensors)
+        dnn, dnn_linear_w, out_bias = (tensors[:-2], tensors[-2], tensors[-1]) if len(tensors) > 1 else ((), None, tensors[-1])
+        d = _fmhead_desc(emb, dense, linear_logit, cfg, dnn, dnn_linear_w, out_bias)
+        saved = torch.empty(_native_size(lib.satrans_fmhead_saved_floats, d), dtype=torch.float32, device=dev)
+        logit = torch.empty(emb.shape[0], 1, dtype=torch.float32, device=dev)
+        N.check(lib.satrans_fmhead_fwd(C.byref(d), logit.data_ptr(), saved.data_ptr(), N.stream_handle(dev)), "satrans_fmhead_fwd")
+        ctx.cfg, ctx.has_dense, ctx.has_lin = cfg, dense is not None, linear_logit is not None
+        ctx.save_for_backward(emb, saved, *tensors, *(() if dense is None else (dense,)))
+        ctx.mark_non_differentiable(saved)
+        return logit, saved
+
+    @staticmethod
+    def backward(ctx, dlogit, _dsaved):
+        lib = N.lib()
+        emb, saved, *rest = ctx.saved_tensors
+        dense = rest.pop() if ctx.has_dense else None
+        dnn, dnn_linear_w, out_bias = (tuple(rest[:-2]), rest[-2], rest[-1]) if len(rest) > 1 else ((), None, rest[-1])
+        dlogit = dlogit.contiguous()
+        d = _fmhead_desc(emb, dense, None, ctx.cfg, dnn, dnn_linear_w, out_bias)
+        work = torch.empty(_native_size(lib.satrans_fmhead_workspace_floats, d), dtype=torch.float32, device=emb.device)
+        demb = torch.empty_like(emb)
+        ddense = None if dense is None else torch.empty_like(dense)
+        grads = [torch.empty_like(t) for t in rest]
+        g = _fmhead_fill(N.FMHeadGrads(), len(dnn) // 2, grads[:-2], grads[-2] if dnn else None, grads[-1])
+        N.check(lib.satrans_fmhead_bwd(C.byref(d), dlogit.data_ptr(), demb.data_ptr(), None if ddense is None else ddense.data_ptr(),
+                                       saved.data_ptr(), work.data_ptr(), C.byref(g), N.stream_handle(emb.device)),
+                "satrans_fmhead_bwd")
+        return (demb, ddense, dlogit if ctx.has_lin else None, None, *grads)
+
+
+class _FMFamilyHead(nn.Module):
+    """What DeepFMHead and NFMHead share: the checks of a call, the DNN's parameters in the reference's order, the
+    regularisation the reference's constructors register themselves."""
+
+    def _init_dnn(self, what, n_in, dnn_hidden_units, l2_reg_dnn, init_std, refused):
+        if refused:
+            raise NotImplementedError(f"{what}: dropout, batch-norm and activations other than relu are not built")
+        units = [int(u) for u in dnn_hidden_units]
+        if len(units) > N.MMOE_MAX_HIDDEN:
+            raise NotImplementedError(f"{what}: up to MMOE_MAX_HIDDEN = {N.MMOE_MAX_HIDDEN} hidden layers, got {len(units)}")
+        self.l2_reg_dnn = float(l2_reg_dnn)
+        # (first: in the reference's state_dict `out.*` precedes the model's own modules, because its BaseModel registers that name)
+        self.out = _OutBias()
+        self.use_dnn = len(units) > 0
+        if self.use_dnn:
+            self.dnn = _TowerDNN(n_in, units, init_std)
+            self.dnn_linear = nn.Linear(units[-1], 1, bias=False)
+
+    @staticmethod
+    def _check_sizes(what, field_size, embedding_size, dense_dim):
+        if field_size is not None and field_size < 2:
+            raise ValueError(f"{what}: field_size must be at least 2 (one pair)")
+        if embedding_size < 1 or dense_dim < 0:
+            raise ValueError(f"{what}: embedding_size must be positive, dense_dim non-negative")
+        if field_size is not None and field_size > N.FM_MAX_FIELDS:
+            raise NotImplementedError(f"{what}: up to FM_MAX_FIELDS = {N.FM_MAX_FIELDS} fields, got {field_size}")
+        if embedding_size > N.FM_MAX_DIM:
+            raise NotImplementedError(f"{what}: embedding_size up to FM_MAX_DIM = {N.FM_MAX_DIM}, got {embedding_size}")
+
+    def regularization_loss(self):
+        total = torch.zeros((1,), device=self.out.bias.device)
+        if self.l2_reg_dnn > 0 and self.use_dnn:
+            for p in [lin.weight for lin in self.dnn.linears] + [self.dnn_linear.weight]:
+                total = total + torch.sum(self.l2_reg_dnn * torch.square(p))
+        return total
+
+    def _run(self, what, emb, dense, linear_logit, cfg):
+        if emb.dim() != 3 or emb.shape[2] != self.embedding_size or emb.shape[1] < 2 or \
+                (self.field_size is not None and emb.shape[1] != self.field_size):
+            raise ValueError(f"{what}: expected emb [B, {self.field_size or 'F >= 2'}, {self.embedding_size}], got {tuple(emb.shape)}")
+        got = 0 if dense is None else (dense.shape[1] if dense.dim() == 2 else -1)
+        if got != self.dense_dim:
+            raise ValueError(f"{what}: expected dense [B, {self.dense_dim}], got {None if dense is None else tuple(dense.shape)}")
+        if linear_logit is not None and tuple(linear_logit.shape) != (emb.shape[0], 1):
+            raise ValueError(f"{what}: expected linear_logit [B, 1], got {tuple(linear_logit.shape)}")
+        N.require_gpu(emb, what)
+        if emb.dtype != torch.float32 or self.out.bias.dtype != torch.float32:
+            raise TypeError(f"{what}: rows, parameters and gradients are float32")
+        if emb.shape[1] > N.FM_MAX_FIELDS:
+            raise NotImplementedError(f"{what}: up to FM_MAX_FIELDS = {N.FM_MAX_FIELDS} fields, got {emb.shape[1]}")
+        tensors = [self.out.bias]
+        if self.use_dnn:
+            tensors = ([lin.weight for lin in self.dnn.linears] + [lin.bias for lin in self.dnn.linears] +
+                       [self.dnn_linear.weight, self.out.bias])
+        logit, _ = _FMHeadFn.apply(emb, dense if self.dense_dim and self.use_dnn else None, linear_logit, cfg, *tensors)
+        return logit
+
+
+class DeepFMHead(_FMFamilyHead):
+    """The half of the reference's DeepFM.forward behind the embedding lookup (models/deepfm.py:87-113):
+
+        logit = linear_logit + FM(emb) (use_fm) + dnn_linear(dnn(cat(flatten(emb), dense))) (hidden units non-empty) + out.bias
+
+    forward(emb [B, field_size, embedding_size] fp32, dense [B, dense_dim] or None, linear_logit [B, 1] or None) -> logit
+    [B, 1]; the caller applies the sigmoid.  `linear_logit` is the port's own linear_model(X), as in XDeepFMHead; its gradient is
+    the logit's.  use_fm=False serves the reference's `nofm` flag; empty dnn_hidden_units its `nodnn` flag, and then there are no
+    dnn.* entries (and the dense values are not read); both off: ValueError.  The reference's `metatrans` flag transforms the
+    embedding block first:
+
+        head = DeepFMHead(F, D, dense_dim, ...); meta = MetaTransformation(D, num_domains)
+        logit = head(meta(domain_ids, emb), dense, linear_logit)
+
+    The whole head is ONE autograd.Function over satrans_fmhead_fwd / satrans_fmhead_bwd (csrc/fm.hip): one pass over the rows
+    writes the FM term and linear_logit into the logit and the rows into the DNN input, the DNN runs on the dense layer launcher
+    of csrc/head_layers.h and adds its column, and the embedding gradient is written once, the DNN input gradient's block plus
+    the FM term.  Parameter names, state_dict order and initialisation are the reference DeepFM's: out.bias (zeros),
+    dnn.linears.{l}.{weight,bias} (weights N(0, init_std)), dnn_linear.weight.  regularization_loss() -> [1] is what
+    DeepFM.__init__ itself registers (deepfm.py:66-68): l2_reg_dnn times the squares of the DNN's weights and of
+    dnn_linear.weight, in get_regularization_loss's arithmetic.
+    Not built: a DeepFM model class behind BaseModel; dropout, batch-norm and activations other than relu (NotImplementedError);
+    bf16; more than MMOE_MAX_HIDDEN hidden layers, FM_MAX_FIELDS fields, an embedding size beyond FM_MAX_DIM."""
+
+    def __init__(self, field_size, embedding_size, dense_dim=0, use_fm=True, dnn_hidden_units=(256, 128), l2_reg_dnn=0,
+                 init_std=0.0001, dnn_dropout=0, dnn_activation='relu', dnn_use_bn=False):
+        super().__init__()
+        self._check_sizes("DeepFMHead", field_size, embedding_size, dense_dim)
+        if not use_fm and len(dnn_hidden_units) == 0:
+            raise ValueError("DeepFMHead: neither the FM term nor a DNN")
+        self.field_size, self.embedding_size, self.dense_dim = int(field_size), int(embedding_size), int(dense_dim)
+        self.use_fm = bool(use_fm)
+        self._init_dnn("DeepFMHead", self.field_size * self.embedding_size + self.dense_dim, dnn_hidden_units, l2_reg_dnn, init_std,
+                       dnn_dropout != 0 or dnn_activation != 'relu' or dnn_use_bn)
+        if self.use_fm:
+            self.fm = FM()
+
+    def forward(self, emb, dense=None, linear_logit=None):
+        return self._run("DeepFMHead", emb, dense, linear_logit, (N.FMHEAD_DEEPFM, int(self.use_fm)))
+
+
+class NFMHead(_FMFamilyHead):
+    """The half of the reference's NFM.forward behind the embedding lookup (models/nfm.py:73-83):
+
+        logit = linear_logit + dnn_linear(dnn(cat(BiInteractionPooling(emb)[:, 0, :], dense))) + out.bias
+
+    forward(emb [B, F, embedding_size] fp32 (any 2 <= F <= FM_MAX_FIELDS), dense [B, dense_dim] or None, linear_logit [B, 1] or
+    None) -> logit [B, 1]; the caller applies the sigmoid.  With the reference's `metatrans` flag:
+
+        head = NFMHead(D, dense_dim, ...); meta = MetaTransformation(D, num_domains)
+        logit = head(meta(domain_ids, emb), dense, linear_logit)
+
+    ONE autograd.Function over satrans_fmhead_fwd / satrans_fmhead_bwd (csrc/fm.hip): the pooled row goes straight into the DNN
+    input, the DNN runs on the dense layer launcher of csrc/head_layers.h, and the embedding gradient is written once from the
+    DNN input gradient.  Parameter names, state_dict order and initialisation are the reference NFM's: out.bias,
+    dnn.linears.{l}.{weight,bias}, dnn_linear.weight; regularization_loss() is what NFM.__init__ registers (nfm.py:53-55).
+    Not built: bi_dropout, dnn_dropout, activations other than relu (NotImplementedError); empty dnn_hidden_units (ValueError:
+    the reference's constructor fails there too); bf16; the limits of DeepFMHead."""
+
+    def __init__(self, embedding_size, dense_dim=0, dnn_hidden_units=(128, 128), l2_reg_dnn=0, init_std=0.0001, bi_dropout=0,
+                 dnn_dropout=0, dnn_activation='relu'):
+        super().__init__()
+        self._check_sizes("NFMHead", None, embedding_size, dense_dim)
+        if len(dnn_hidden_units) == 0:
+            raise ValueError("NFMHead: dnn_hidden_units must not be empty")
+        self.field_size, self.embedding_size, self.dense_dim = None, int(embedding_size), int(dense_dim)
+        self._init_dnn("NFMHead", self.embedding_size + self.dense_dim, dnn_hidden_units, l2_reg_dnn, init_std,
+                       bi_dropout != 0 or dnn_dropout != 0 or dnn_activation != 'relu')
+        self.bi_pooling = BiInteractionPooling()
+
+    def forward(self, emb, dense=None, linear_logit=None):
+        return self._run("NFMHead", emb, dense, linear_logit, (N.FMHEAD_NFM, 0))
+
+
+class AFMHead(nn.Module):
+    """The half of the reference's AFM.forward behind the embedding lookup (models/afm.py:66-73) with use_attention=True:
+
+        logit = linear_logit + fm(emb) + out.bias,   fm = AFMLayer(embedding_size, attention_factor)
+
+    forward(emb [B, F, embedding_size] fp32 or deepctr's list of pieces, linear_logit [B, 1] or None) -> logit [B, 1]; the
+    caller applies the sigmoid.  linear_logit and out.bias enter in the AFM forward's epilogue, so the head is the same two
+    launches as the layer; `fm.normalized_att_score` is set as by the layer.  With the reference's `metatrans` flag:
+
+        head = AFMHead(D, ...); meta = MetaTransformation(D, num_domains)
+        logit = head(meta(domain_ids, emb), linear_logit)
+
+    state_dict keys in the reference's order: out.bias, fm.attention_W, fm.attention_b, fm.projection_h, fm.projection_p.
+    regularization_loss() -> [1] is what AFM.__init__ registers (afm.py:49): l2_reg_att times the sum of squares of
+    fm.attention_W.  use_attention=False is DeepFMHead(field_size, embedding_size, use_fm=True, dnn_hidden_units=()).
+    Not built: afm_dropout (NotImplementedError); the limits of AFMLayer."""
+
+    def __init__(self, embedding_size, attention_factor=8, l2_reg_att=1e-5, afm_dropout=0):
+        super().__init__()
+        if afm_dropout != 0:
+            raise NotImplementedError("AFMHead: dropout is not built")
+        self.embedding_size, self.l2_reg_att = int(embedding_size), float(l2_reg_att)
+        # (first: in the reference's state_dict `out.*` precedes AFM's own modules, because its BaseModel registers that name)
+        self.out = _OutBias()
+        self.fm = AFMLayer(self.embedding_size, attention_factor, l2_reg_att, afm_dropout)
+
+    def regularization_loss(self):
+        total = torch.zeros((1,), device=self.out.bias.device)
+        if self.l2_reg_att > 0:
+            total = total + torch.sum(self.l2_reg_att * torch.square(self.fm.attention_W))
+        return total
+
+    def forward(self, emb, linear_logit=None):
+        if linear_logit is not None and (linear_logit.dim() != 2 or linear_logit.shape[1] != 1):
+            raise ValueError(f"AFMHead: expected linear_logit [B, 1], got {tuple(linear_logit.shape)}")
+        return self.fm._run(emb, linear_logit, self.out.bias, "AFMHead")

@@ -299,6 +299,50 @@ class PNNGrads(C.Structure):
     _fields_ = list(_PNN_POINTER_FIELDS)
 
 
+FM_MAX_FIELDS = 64               # SATRANS_FM_MAX_FIELDS
+FM_MAX_DIM = 128                 # SATRANS_FM_MAX_DIM: the embedding size
+AFM_MAX_FACTOR = 64              # SATRANS_AFM_MAX_FACTOR: the attention factor A
+AFM_MAX_WORKGROUPS = 1024        # SATRANS_AFM_MAX_WORKGROUPS: partials of AFM's parameter gradients at most
+FMHEAD_DEEPFM, FMHEAD_NFM = 0, 1      # SATRANS_FMHEAD_*
+
+
+class FMDesc(C.Structure):
+    """Mirror of `satrans_fm_desc` (FM and BiInteractionPooling)."""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("reserved", C.c_int32), ("e", _vp)]
+
+
+# the parameter pointers of satrans_afm_desc / satrans_afm_grads in the header's order
+AFM_POINTERS = ("attention_W", "attention_b", "projection_h", "projection_p")
+
+
+class AFMDesc(C.Structure):
+    """Mirror of `satrans_afm_desc`."""
+    _fields_ = ([("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("A", C.c_int32), ("e", _vp)] +
+                [(name, _vp) for name in AFM_POINTERS] + [("linear_logit", _vp), ("out_bias", _vp)])
+
+
+class AFMGrads(C.Structure):
+    """Mirror of `satrans_afm_grads`."""
+    _fields_ = [(name, _vp) for name in AFM_POINTERS] + [("out_bias", _vp)]
+
+
+# the parameter pointers of satrans_fmhead_desc / satrans_fmhead_grads in the header's order: (name, per hidden layer)
+FMHEAD_POINTERS = (("dnn_w", True), ("dnn_b", True), ("dnn_linear_w", False), ("out_bias", False))
+_FMHEAD_POINTER_FIELDS = [(name, _vp * MMOE_MAX_HIDDEN if per_layer else _vp) for name, per_layer in FMHEAD_POINTERS]
+
+
+class FMHeadDesc(C.Structure):
+    """Mirror of `satrans_fmhead_desc` (DeepFM's and NFM's heads; the DNN's layer limit is MMOE_MAX_HIDDEN)."""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("kind", C.c_int32), ("use_fm", C.c_int32),
+                ("dense_dim", C.c_int32), ("n_dnn", C.c_int32), ("reserved", C.c_int32), ("width", C.c_int32 * MMOE_MAX_HIDDEN),
+                ("reserved2", C.c_int32), ("emb", _vp), ("dense", _vp), ("linear_logit", _vp)] + _FMHEAD_POINTER_FIELDS
+
+
+class FMHeadGrads(C.Structure):
+    """Mirror of `satrans_fmhead_grads`."""
+    _fields_ = list(_FMHEAD_POINTER_FIELDS)
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -439,6 +483,18 @@ SIGNATURES = {
     "satrans_pnn_workspace_floats": (C.c_int64, [C.POINTER(PNNDesc)]),
     "satrans_pnn_fwd": (C.c_int, [C.POINTER(PNNDesc), _vp, _vp, _vp]),
     "satrans_pnn_bwd": (C.c_int, [C.POINTER(PNNDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(PNNGrads), _vp]),
+    "satrans_fm_fwd": (C.c_int, [C.POINTER(FMDesc), _vp, _vp]),
+    "satrans_fm_bwd": (C.c_int, [C.POINTER(FMDesc), _vp, _vp, _vp]),
+    "satrans_bipool_fwd": (C.c_int, [C.POINTER(FMDesc), _vp, _vp]),
+    "satrans_bipool_bwd": (C.c_int, [C.POINTER(FMDesc), _vp, _vp, _vp]),
+    "satrans_afm_saved_floats": (C.c_int64, [C.POINTER(AFMDesc)]),
+    "satrans_afm_workspace_floats": (C.c_int64, [C.POINTER(AFMDesc)]),
+    "satrans_afm_fwd": (C.c_int, [C.POINTER(AFMDesc), _vp, _vp, _vp]),
+    "satrans_afm_bwd": (C.c_int, [C.POINTER(AFMDesc), _vp, _vp, _vp, _vp, C.POINTER(AFMGrads), _vp]),
+    "satrans_fmhead_saved_floats": (C.c_int64, [C.POINTER(FMHeadDesc)]),
+    "satrans_fmhead_workspace_floats": (C.c_int64, [C.POINTER(FMHeadDesc)]),
+    "satrans_fmhead_fwd": (C.c_int, [C.POINTER(FMHeadDesc), _vp, _vp, _vp]),
+    "satrans_fmhead_bwd": (C.c_int, [C.POINTER(FMHeadDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(FMHeadGrads), _vp]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
