@@ -45,7 +45,8 @@ extern "C" {
  *    satrans_cross_grads, satrans_cross_*), and FiBiNET's SENet, bilinear interaction and head (satrans_senet_*,
  *    satrans_bilinear_*, satrans_fibinet_*), and PNN's inner and outer product layers and head (satrans_inner_product_*,
  *    satrans_outer_product_*, satrans_pnn_*), and FM, BiInteractionPooling, AFM and the DeepFM / NFM heads (satrans_fm_*,
- *    satrans_bipool_*, satrans_afm_*, satrans_fmhead_*). */
+ *    satrans_bipool_*, satrans_afm_*, satrans_fmhead_*), and AutoInt's interacting layer and head (satrans_interacting_*,
+ *    satrans_autoint_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -1025,6 +1026,71 @@ int64_t satrans_fmhead_workspace_floats(const satrans_fmhead_desc* d);
 int satrans_fmhead_fwd(const satrans_fmhead_desc* d, float* logit, float* saved, void* stream);
 int satrans_fmhead_bwd(const satrans_fmhead_desc* d, const float* dlogit, float* demb, float* ddense, const float* saved,
                        float* workspace, const satrans_fmhead_grads* g, void* stream);
+
+/* InteractingLayer of deepctr-torch 0.2.9, which the reference's models/autoint.py builds (autoint.py:13,75-76), and the half of
+ * AutoInt.forward behind the lookup (autoint.py:93-121).  It is NOT satrans_selfatt_*: no W_Out, no dropout, no LayerNorm.
+ * x [B, F, D], H heads of dh = D / H columns, weights [D, D] applied as x W:
+ *     q, k, v, r = x W_Query, x W_key, x W_Value, x W_Res;   p = softmax_j(q_i . k_j (/ sqrt(dh) unless SATRANS_NO_SCALING)) per
+ *     (sample, head);   y = relu(p v + r)   (no r with SATRANS_NO_RES, and then w_res is not read)
+ *     AUTOINT   logit = [ flatten(layer_L(... layer_1(emb))) | dnn([ flatten(emb) | dense ]) ] dnn_linear_w^T + out_bias
+ *               (without a DNN, n_dnn = 0: the first block alone, and dense is not read)
+ * fp32 throughout.  D in {16, 32, 64}, dh in {8, 16, 32}, 2 <= F <= 64, any B >= 1; the size functions return -1 for anything else
+ * and the launches SATRANS_E_UNSUPPORTED, decided before a device is touched.
+ * satrans_interacting_fwd: one launch.  y [B, F, D]; att (or null) [H, B, F, F], deepctr's normalized_att_scores; saved = the
+ * softmax rows' (max, sum): 2 B H F floats, all written.  satrans_interacting_bwd takes y (for the relu mask) and dy, recomputes q, k, v from
+ * d->x, WRITES dx [B, F, D] and g_w = the gradients of W_Query, W_key, W_Value (, W_Res) as one [3 or 4, D, D] block; scratch is
+ * one such block per workgroup, at most SATRANS_INTERACTING_MAX_WORKGROUPS of them, merged in workgroup order.
+ * satrans_autoint_fwd: logit [B, 1]; att (or null): n_layers pointers, each null or [H, B, F, F]; saved = the layers' outputs
+ * [n_layers, B, F, D], their statistics, and with a DNN its input [B, F D + dense_dim] and hidden rows.  satrans_autoint_bwd
+ * WRITES demb [B, F, D], ddense [B, dense_dim] (null when dense_dim = 0 or without a DNN) and every gradient of g; g->int_w[l]
+ * is layer l's [3 or 4, D, D] block.
+ * No floating-point atomics: equal inputs give equal bits, and a sample's y / logit are the same bits alone as inside a batch. */
+#define SATRANS_INTERACTING_MAX_WORKGROUPS 512
+#define SATRANS_AUTOINT_MAX_LAYERS 8
+typedef struct satrans_interacting_desc {
+    int32_t B, F, D, H;
+    uint32_t flags;                         /* SATRANS_NO_RES, SATRANS_NO_SCALING */
+    int32_t reserved;
+    const float* x;                         /* [B, F, D] */
+    const float* w_query;                   /* [D, D] */
+    const float* w_key;
+    const float* w_value;
+    const float* w_res;                     /* null with SATRANS_NO_RES */
+} satrans_interacting_desc;
+int64_t satrans_interacting_saved_floats(const satrans_interacting_desc* d);
+int64_t satrans_interacting_scratch_floats(const satrans_interacting_desc* d);
+int satrans_interacting_fwd(const satrans_interacting_desc* d, float* y, float* att, float* saved, void* stream);
+int satrans_interacting_bwd(const satrans_interacting_desc* d, const float* y, const float* dy, float* dx, const float* saved,
+                            float* scratch, float* g_w, void* stream);
+typedef struct satrans_autoint_desc {
+    int32_t B, F, D, H;
+    uint32_t flags;                         /* SATRANS_NO_RES, SATRANS_NO_SCALING */
+    int32_t n_layers, dense_dim, n_dnn;
+    int32_t width[SATRANS_MMOE_MAX_HIDDEN];
+    int32_t reserved;
+    const float* emb;                       /* [B, F, D] */
+    const float* dense;                     /* [B, dense_dim], null when dense_dim = 0 */
+    const float* w_query[SATRANS_AUTOINT_MAX_LAYERS];
+    const float* w_key[SATRANS_AUTOINT_MAX_LAYERS];
+    const float* w_value[SATRANS_AUTOINT_MAX_LAYERS];
+    const float* w_res[SATRANS_AUTOINT_MAX_LAYERS];
+    const float* dnn_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* dnn_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* dnn_linear_w;              /* [1, F D + last width] (n_dnn = 0: [1, F D]) */
+    const float* out_bias;                  /* [1] */
+} satrans_autoint_desc;
+typedef struct satrans_autoint_grads {
+    float* int_w[SATRANS_AUTOINT_MAX_LAYERS];
+    float* dnn_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* dnn_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* dnn_linear_w;
+    float* out_bias;
+} satrans_autoint_grads;
+int64_t satrans_autoint_saved_floats(const satrans_autoint_desc* d);
+int64_t satrans_autoint_workspace_floats(const satrans_autoint_desc* d);
+int satrans_autoint_fwd(const satrans_autoint_desc* d, float* logit, float* const* att, float* saved, void* stream);
+int satrans_autoint_bwd(const satrans_autoint_desc* d, const float* dlogit, float* demb, float* ddense, const float* saved,
+                        float* workspace, const satrans_autoint_grads* g, void* stream);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

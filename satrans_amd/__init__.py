@@ -4,9 +4,9 @@ from .inputs import DenseFeat, SparseFeat, VarLenSparseFeat, build_input_feature
 from .callbacks import History  # noqa: F401
 from .basemodel import BaseModel  # noqa: F401
 from .satrans import SATrans  # noqa: F401
-from .layers import (CIN, FM, AdaSparseHead, AFMHead, AFMLayer, BiInteractionPooling, BilinearInteraction, CrossNet,  # noqa: F401
-                     DCNHead, DeepFMHead, FiBiNETHead, InnerProductLayer, MDR_BatchNorm, MetaTransformation, MMoEHead, NFMHead,
-                     OutterProductLayer, PartitionedNorm, PLEHead, PNNHead, PrunedDNN, SelfAttention_Layer, SENETLayer,
+from .layers import (CIN, FM, AdaSparseHead, AFMHead, AFMLayer, AutoIntHead, BiInteractionPooling, BilinearInteraction,  # noqa: F401
+                     CrossNet, DCNHead, DeepFMHead, FiBiNETHead, InnerProductLayer, InteractingLayer, MDR_BatchNorm,
+                     MetaTransformation, MMoEHead, NFMHead, OutterProductLayer, PartitionedNorm, PLEHead, PNNHead, PrunedDNN, SelfAttention_Layer, SENETLayer,
                      SharedBottomHead, StarHead, StarTowers, XDeepFMHead)
 
 __all__ = ["SATrans", "BaseModel", "SparseFeat", "DenseFeat", "VarLenSparseFeat", "get_feature_names",
@@ -14,4 +14,4 @@ __all__ = ["SATrans", "BaseModel", "SparseFeat", "DenseFeat", "VarLenSparseFeat"
            "MDR_BatchNorm", "PartitionedNorm", "StarTowers", "StarHead", "MMoEHead", "PLEHead", "PrunedDNN", "AdaSparseHead",
            "SharedBottomHead", "CIN", "XDeepFMHead", "CrossNet", "DCNHead", "SENETLayer", "BilinearInteraction", "FiBiNETHead",
            "InnerProductLayer", "OutterProductLayer", "PNNHead", "FM", "BiInteractionPooling", "AFMLayer", "DeepFMHead", "NFMHead",
-           "AFMHead"]
+           "AFMHead", "InteractingLayer", "AutoIntHead"]

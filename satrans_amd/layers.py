@@ -51,8 +51,15 @@
     exists; and `DeepFMHead`, `NFMHead` and `AFMHead`, the parts of the three forwards behind the embeddings (deepfm.py:87-113,
     nfm.py:73-83, afm.py:66-73) with linear_logit and out.bias, each head one autograd.Function (csrc/fm.hip).
 
+  * `InteractingLayer` - deepctr's interacting layer, which the reference's AutoInt stacks (models/autoint.py:13,75-76; NOT
+    SelfAttention_Layer: W_Query, W_key, W_Value, W_Res only, scaling off by default, relu(o + x W_Res) as the tail): one launch
+    forward, one plus an ordered reduce backward, whole samples held on chip, only the softmax rows' (max, sum) saved; and
+    `AutoIntHead`, the part of AutoInt.forward behind the embeddings (autoint.py:93-121), the whole head one autograd.Function
+    (csrc/autoint.hip).
+
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
-csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip, csrc/fibinet.hip, csrc/pnn.hip, csrc/fm.hip) wrapped
+csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip, csrc/fibinet.hip, csrc/pnn.hip, csrc/fm.hip,
+csrc/autoint.hip) wrapped
 in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
@@ -2581,3 +2588,263 @@ class AFMHead(nn.Module):
         if linear_logit is not None and (linear_logit.dim() != 2 or linear_logit.shape[1] != 1):
             raise ValueError(f"AFMHead: expected linear_logit [B, 1], got {tuple(linear_logit.shape)}")
         return self.fm._run(emb, linear_logit, self.out.bias, "AFMHead")
+
+
+def _interacting_flags(use_res, scaling):
+    return (0 if use_res else N.NO_RES) | (0 if scaling else NO_SCALING)
+
+
+def _interacting_desc(x, head_num, flags, weights):
+    d = N.InteractingDesc()
+    d.B, d.F, d.D = x.shape
+    d.H, d.flags, d.x = head_num, flags, x.data_ptr()
+    for name, w in zip(N.INTERACTING_POINTERS, weights):
+        setattr(d, name, w.data_ptr())
+    return d
+
+
+class _InteractingFn(torch.autograd.Function):
+    """y [B, F, D] of one InteractingLayer (csrc/autoint.hip).  cfg = (head_num, flags, capture); `weights`: W_Query, W_key,
+    W_Value (, W_Res).  `saved` = the softmax rows' (max, sum), 2 B H F floats; `att` = the normalised scores [H, B, F, F]
+    (empty unless capture)."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, *weights):
+        lib = N.lib()
+        head_num, flags, capture = cfg
+        x = x.contiguous()
+        weights = tuple(w.contiguous() for w in weights)
+        d = _interacting_desc(x, head_num, flags, weights)
+        n = int(lib.satrans_interacting_saved_floats(C.byref(d)))
+        if n < 0:
+            raise N.NativeError(f"InteractingLayer: shape B={d.B} F={d.F} D={d.D} H={head_num} is not supported")
+        saved = torch.empty(n, dtype=torch.float32, device=x.device)
+        y = torch.empty_like(x)
+        att = torch.empty((head_num, d.B, d.F, d.F) if capture else (0,), dtype=torch.float32, device=x.device)
+        N.check(lib.satrans_interacting_fwd(C.byref(d), y.data_ptr(), att.data_ptr() if capture else None, saved.data_ptr(),
+                                            N.stream_handle(x.device)), "satrans_interacting_fwd")
+        ctx.cfg = cfg
+        ctx.save_for_backward(x, y, saved, *weights)
+        ctx.mark_non_differentiable(saved, att)
+        return y, saved, att
+
+    @staticmethod
+    def backward(ctx, dy, _dsaved, _datt):
+        lib = N.lib()
+        x, y, saved, *weights = ctx.saved_tensors
+        d = _interacting_desc(x, ctx.cfg[0], ctx.cfg[1], weights)
+        scratch = torch.empty(_native_size(lib.satrans_interacting_scratch_floats, d), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        g = torch.empty(len(weights), d.D, d.D, dtype=torch.float32, device=x.device)
+        N.check(lib.satrans_interacting_bwd(C.byref(d), y.data_ptr(), dy.contiguous().data_ptr(), dx.data_ptr(), saved.data_ptr(),
+                                            scratch.data_ptr(), g.data_ptr(), N.stream_handle(x.device)), "satrans_interacting_bwd")
+        return (dx, None, *g.unbind(0))
+
+
+class InteractingLayer(nn.Module):
+    """deepctr-torch 0.2.9's InteractingLayer, the layer the reference's AutoInt stacks (models/autoint.py:13,75-76), with
+    deepctr's constructor, its two ValueErrors, its parameter names (`W_key` has a lower-case k) and creation order - W_Query,
+    W_key, W_Value, W_Res (with use_res) - every one drawn N(0, 0.05):
+
+        q, k, v = x W_Query, x W_key, x W_Value;   per head h of D / head_num columns:  p = softmax_j(q_i . k_j), divided by
+        sqrt(D / head_num) first with scaling (deepctr's default: off);   y = relu(p v + x W_Res)   (no residual: relu(p v))
+
+    It is not SelfAttention_Layer (the reference's submodules.py:178-238): no W_Out, no dropout, no LayerNorm, `scaling`
+    defaults to False, and a checkpoint of one does not load into the other.
+    forward(inputs [B, F, D] fp32 on the GPU) -> [B, F, D]: ONE autograd.Function, one launch forward (satrans_interacting_fwd,
+    csrc/autoint.hip), one launch plus an ordered reduce backward.  Only the softmax rows' (max, sum) are saved: 2 B H F floats;
+    the backward recomputes q, k, v from the input and takes the relu mask from the output.
+    `capture_attention` (default False) makes the forward also write `normalized_att_scores` [H, B, F, F], the switch
+    SelfAttention_Layer has; deepctr fills that attribute on every forward, here it stays None until the switch is on.
+    Shapes: D in {16, 32, 64}, D / head_num in {8, 16, 32}, 2 <= F <= 64; anything else raises NativeError at the call."""
+
+    def __init__(self, embedding_size, head_num=2, use_res=True, scaling=False, seed=1024, device='cpu'):
+        super().__init__()
+        if head_num <= 0:
+            raise ValueError('head_num must be a int > 0')
+        if embedding_size % head_num != 0:
+            raise ValueError('embedding_size is not an integer multiple of head_num!')
+        self.att_embedding_size = embedding_size // head_num
+        self.head_num, self.use_res, self.scaling, self.seed = head_num, use_res, scaling, seed
+        self.W_Query = nn.Parameter(torch.Tensor(embedding_size, embedding_size))
+        self.W_key = nn.Parameter(torch.Tensor(embedding_size, embedding_size))
+        self.W_Value = nn.Parameter(torch.Tensor(embedding_size, embedding_size))
+        if self.use_res:
+            self.W_Res = nn.Parameter(torch.Tensor(embedding_size, embedding_size))
+        for tensor in self.parameters():
+            nn.init.normal_(tensor, mean=0.0, std=0.05)
+        self.normalized_att_scores = None
+        self.capture_attention = False
+        self.to(device)
+
+    def weights(self):
+        return [self.W_Query, self.W_key, self.W_Value] + ([self.W_Res] if self.use_res else [])
+
+    def forward(self, inputs):
+        if len(inputs.shape) != 3:
+            raise ValueError("Unexpected inputs dimensions %d, expect to be 3 dimensions" % (len(inputs.shape)))
+        if inputs.shape[2] != self.W_Query.shape[0]:
+            raise ValueError(f"InteractingLayer: expected an embedding size of {self.W_Query.shape[0]}, got {tuple(inputs.shape)}")
+        N.require_gpu(inputs, "InteractingLayer")
+        if inputs.dtype != torch.float32 or self.W_Query.dtype != torch.float32:
+            raise TypeError("InteractingLayer: inputs, parameters and gradients are float32")
+        cfg = (self.head_num, _interacting_flags(self.use_res, self.scaling), bool(self.capture_attention))
+        y, _, att = _InteractingFn.apply(inputs, cfg, *self.weights())
+        if self.capture_attention:
+            self.normalized_att_scores = att
+        return y
+
+
+def _autoint_fill(tgt, n_dnn, dnn, dnn_linear_w, out_bias):
+    """Set the DNN pointers of a satrans_autoint_desc / satrans_autoint_grads; `dnn`: the weights, then the biases."""
+    for l in range(n_dnn):
+        tgt.dnn_w[l], tgt.dnn_b[l] = dnn[l].data_ptr(), dnn[n_dnn + l].data_ptr()
+    tgt.dnn_linear_w, tgt.out_bias = dnn_linear_w.data_ptr(), out_bias.data_ptr()
+    return tgt
+
+
+def _autoint_desc(emb, dense, cfg, int_w, dnn, dnn_linear_w, out_bias):
+    head_num, flags, n_layers = cfg[:3]
+    n_dnn = len(dnn) // 2
+    d = _autoint_fill(N.AutoIntDesc(), n_dnn, dnn, dnn_linear_w, out_bias)
+    d.B, d.F, d.D = emb.shape
+    d.H, d.flags, d.n_layers = head_num, flags, n_layers
+    d.dense_dim, d.n_dnn = 0 if dense is None else dense.shape[1], n_dnn
+    for l in range(n_dnn):
+        d.width[l] = dnn[l].shape[0]
+    d.emb, d.dense = emb.data_ptr(), None if dense is None else dense.data_ptr()
+    per = len(int_w) // n_layers
+    for l in range(min(n_layers, N.AUTOINT_MAX_LAYERS)):
+        for name, w in zip(N.INTERACTING_POINTERS, int_w[l * per:(l + 1) * per]):
+            getattr(d, name)[l] = w.data_ptr()
+    return d
+
+
+class _AutoIntFn(torch.autograd.Function):
+    """logit [B, 1] of the AutoInt head (csrc/autoint.hip).  cfg = (head_num, flags, n_layers, capture: a tuple of bools);
+    `tensors`: the layers' weights layer by layer, the DNN's weights, its biases, dnn_linear's weight, out.bias.  `saved` = the
+    layers' outputs, their softmax statistics, the DNN input, the DNN's hidden rows; `atts`: a captured layer's scores."""
+
+    @staticmethod
+    def forward(ctx, emb, dense, cfg, *tensors):
+        lib = N.lib()
+        dev = emb.device
+        head_num, flags, n_layers, capture = cfg
+        emb = emb.contiguous()
+        dense = None if dense is None else dense.contiguous()
+        tensors = tuple(t.contiguous() for t in tensors)
+        n_int = n_layers * (3 if flags & N.NO_RES else 4)
+        int_w, dnn, dnn_linear_w, out_bias = tensors[:n_int], tensors[n_int:-2], tensors[-2], tensors[-1]
+        d = _autoint_desc(emb, dense, cfg, int_w, dnn, dnn_linear_w, out_bias)
+        n = int(lib.satrans_autoint_saved_floats(C.byref(d)))
+        if n < 0:
+            raise N.NativeError(f"AutoIntHead: shape B={d.B} F={d.F} D={d.D} H={head_num} with {n_layers} layers is not supported: "
+                                f"{(lib.satrans_last_error() or b'').decode()}")
+        saved = torch.empty(n, dtype=torch.float32, device=dev)
+        logit = torch.empty(emb.shape[0], 1, dtype=torch.float32, device=dev)
+        atts = [torch.empty((head_num, d.B, d.F, d.F) if on else (0,), dtype=torch.float32, device=dev) for on in capture]
+        ptrs = (C.c_void_p * n_layers)(*[a.data_ptr() if on else None for a, on in zip(atts, capture)])
+        N.check(lib.satrans_autoint_fwd(C.byref(d), logit.data_ptr(), ptrs, saved.data_ptr(), N.stream_handle(dev)), "satrans_autoint_fwd")
+        ctx.cfg, ctx.has_dense, ctx.n_int = cfg, dense is not None, n_int
+        ctx.save_for_backward(emb, saved, *tensors, *(() if dense is None else (dense,)))
+        ctx.mark_non_differentiable(saved, *atts)
+        return (logit, saved, *atts)
+
+    @staticmethod
+    def backward(ctx, dlogit, *_):
+        lib = N.lib()
+        emb, saved, *rest = ctx.saved_tensors
+        dense = rest.pop() if ctx.has_dense else None
+        n_int, n_layers = ctx.n_int, ctx.cfg[2]
+        int_w, dnn, dnn_linear_w, out_bias = rest[:n_int], tuple(rest[n_int:-2]), rest[-2], rest[-1]
+        d = _autoint_desc(emb, dense, ctx.cfg, int_w, dnn, dnn_linear_w, out_bias)
+        work = torch.empty(_native_size(lib.satrans_autoint_workspace_floats, d), dtype=torch.float32, device=emb.device)
+        demb = torch.empty_like(emb)
+        ddense = None if dense is None else torch.empty_like(dense)
+        per = n_int // n_layers
+        g_int = torch.empty(n_layers, per, d.D, d.D, dtype=torch.float32, device=emb.device)
+        grads = [torch.empty_like(t) for t in rest[n_int:]]
+        g = _autoint_fill(N.AutoIntGrads(), len(dnn) // 2, grads[:-2], grads[-2], grads[-1])
+        for l in range(n_layers):
+            g.int_w[l] = g_int[l].data_ptr()
+        N.check(lib.satrans_autoint_bwd(C.byref(d), dlogit.contiguous().data_ptr(), demb.data_ptr(),
+                                        None if ddense is None else ddense.data_ptr(), saved.data_ptr(), work.data_ptr(), C.byref(g),
+                                        N.stream_handle(emb.device)), "satrans_autoint_bwd")
+        return (demb, ddense, None, *g_int.view(n_int, d.D, d.D).unbind(0), *grads)
+
+
+class AutoIntHead(nn.Module):
+    """The half of the reference's AutoInt.forward behind the embedding lookup (models/autoint.py:93-121):
+
+        att_output = flatten(int_layers[L-1](... int_layers[0](emb)))
+        logit = dnn_linear(cat(att_output, dnn(cat(flatten(emb), dense)))) + out.bias     (dnn_hidden_units non-empty)
+        logit = dnn_linear(att_output) + out.bias                                         (dnn_hidden_units=())
+
+    forward(emb [B, field_num, embedding_size] fp32 on the GPU, dense [B, dense_dim] or None) -> logit [B, 1]; the caller
+    applies the sigmoid.  The reference's `logit = 0` holds: its linear model is not added (autoint.py:89-90), so there is no
+    linear_logit argument.  `emb` is the concatenation of the looked-up embeddings of all sparse fields in field order, the
+    domain column included; the reference's `usemetatrans` flag (autoint.py:84-87) transforms that block first and stays the
+    caller's:
+
+        head = AutoIntHead(F, D, dense_dim, ...); meta = MetaTransformation(D, num_domains)
+        logit = head(meta(domain_ids, emb), dense)
+
+    The whole head is ONE autograd.Function over satrans_autoint_fwd / satrans_autoint_bwd (csrc/autoint.hip): one launch per
+    interacting layer each way plus the ordered reduce of its weight gradients, the DNN and both column blocks of dnn_linear on
+    the dense layer launcher of csrc/head_layers.h, and the embedding gradient written once by the first layer's backward with
+    the DNN input gradient added in its epilogue.  `int_layers` are InteractingLayer modules (deepctr's defaults: scaling off), so
+    a layer can be driven alone, and a layer's `capture_attention` makes the head fill its `normalized_att_scores`.
+    state_dict keys and their order are the reference's: out.bias (zeros), dnn_linear.weight (torch's default draw, bias-free),
+    dnn.linears.{l}.{weight,bias} (weights N(0, init_std)), int_layers.{i}.W_Query / W_key / W_Value / W_Res.
+    att_layer_num < 1: ValueError.  Not built: an AutoInt model class behind BaseModel; dropout, batch-norm and activations
+    other than relu in the DNN (NotImplementedError); l2_reg_dnn; bf16; more than AUTOINT_MAX_LAYERS interacting or
+    MMOE_MAX_HIDDEN hidden layers (NotImplementedError); shapes outside InteractingLayer's raise NativeError at the call."""
+
+    def __init__(self, field_num, embedding_size, dense_dim=0, att_layer_num=3, att_head_num=2, att_res=True,
+                 dnn_hidden_units=(256, 128), init_std=0.0001, dnn_dropout=0, dnn_activation='relu', dnn_use_bn=False):
+        super().__init__()
+        if att_layer_num < 1:
+            raise ValueError("AutoIntHead: att_layer_num must be at least 1")
+        if field_num < 2 or embedding_size < 1 or dense_dim < 0:
+            raise ValueError("AutoIntHead: field_num must be at least 2, embedding_size positive, dense_dim non-negative")
+        if dnn_dropout != 0 or dnn_use_bn or dnn_activation != 'relu':
+            raise NotImplementedError("AutoIntHead: dropout, batch-norm and activations other than relu are not built")
+        units = [int(u) for u in dnn_hidden_units]
+        if len(units) > N.MMOE_MAX_HIDDEN:
+            raise NotImplementedError(f"AutoIntHead: up to MMOE_MAX_HIDDEN = {N.MMOE_MAX_HIDDEN} hidden layers, got {len(units)}")
+        if att_layer_num > N.AUTOINT_MAX_LAYERS:
+            raise NotImplementedError(f"AutoIntHead: up to AUTOINT_MAX_LAYERS = {N.AUTOINT_MAX_LAYERS} interacting layers, "
+                                      f"got {att_layer_num}")
+        self.field_num, self.embedding_size, self.dense_dim = int(field_num), int(embedding_size), int(dense_dim)
+        self.att_layer_num, self.att_head_num, self.att_res = int(att_layer_num), int(att_head_num), bool(att_res)
+        n_att = self.field_num * self.embedding_size
+        # (first: in the reference's state_dict `out.*` precedes AutoInt's own modules, because its BaseModel registers that name;
+        # dnn_linear before dnn: autoint.py:66-70)
+        self.out = _OutBias()
+        self.dnn_linear = nn.Linear(n_att + (units[-1] if units else 0), 1, bias=False)
+        self.use_dnn = len(units) > 0
+        if self.use_dnn:
+            self.dnn = _TowerDNN(n_att + self.dense_dim, units, init_std)
+        self.int_layers = nn.ModuleList([InteractingLayer(self.embedding_size, self.att_head_num, self.att_res)
+                                         for _ in range(self.att_layer_num)])
+
+    def forward(self, emb, dense=None):
+        if emb.dim() != 3 or emb.shape[1] != self.field_num or emb.shape[2] != self.embedding_size:
+            raise ValueError(f"AutoIntHead: expected emb [B, {self.field_num}, {self.embedding_size}], got {tuple(emb.shape)}")
+        got = 0 if dense is None else (dense.shape[1] if dense.dim() == 2 else -1)
+        if got != self.dense_dim:
+            raise ValueError(f"AutoIntHead: expected dense [B, {self.dense_dim}], got {None if dense is None else tuple(dense.shape)}")
+        N.require_gpu(emb, "AutoIntHead")
+        if emb.dtype != torch.float32 or self.dnn_linear.weight.dtype != torch.float32:
+            raise TypeError("AutoIntHead: rows, parameters and gradients are float32")
+        capture = tuple(bool(layer.capture_attention) for layer in self.int_layers)
+        cfg = (self.att_head_num, _interacting_flags(self.att_res, self.int_layers[0].scaling), self.att_layer_num, capture)
+        tensors = [w for layer in self.int_layers for w in layer.weights()]
+        if self.use_dnn:
+            tensors += [lin.weight for lin in self.dnn.linears] + [lin.bias for lin in self.dnn.linears]
+        tensors += [self.dnn_linear.weight, self.out.bias]
+        logit, _, *atts = _AutoIntFn.apply(emb, dense if self.dense_dim and self.use_dnn else None, cfg, *tensors)
+        for layer, att, on in zip(self.int_layers, atts, capture):
+            if on:
+                layer.normalized_att_scores = att
+        return logit

@@ -343,6 +343,36 @@ class FMHeadGrads(C.Structure):
     _fields_ = list(_FMHEAD_POINTER_FIELDS)
 
 
+INTERACTING_MAX_WORKGROUPS = 512      # SATRANS_INTERACTING_MAX_WORKGROUPS: partials of a layer's weight gradients at most
+AUTOINT_MAX_LAYERS = 8                # SATRANS_AUTOINT_MAX_LAYERS: interacting layers of a head at most
+# the weight pointers of satrans_interacting_desc / satrans_autoint_desc in the header's order (deepctr's creation order)
+INTERACTING_POINTERS = ("w_query", "w_key", "w_value", "w_res")
+
+
+class InteractingDesc(C.Structure):
+    """Mirror of `satrans_interacting_desc` (deepctr's InteractingLayer; flags: NO_RES, NO_SCALING)."""
+    _fields_ = ([("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("flags", C.c_uint32),
+                 ("reserved", C.c_int32), ("x", _vp)] + [(name, _vp) for name in INTERACTING_POINTERS])
+
+
+# the DNN pointers of satrans_autoint_desc / satrans_autoint_grads in the header's order: (name, per hidden layer)
+AUTOINT_POINTERS = (("dnn_w", True), ("dnn_b", True), ("dnn_linear_w", False), ("out_bias", False))
+_AUTOINT_POINTER_FIELDS = [(name, _vp * MMOE_MAX_HIDDEN if per_layer else _vp) for name, per_layer in AUTOINT_POINTERS]
+
+
+class AutoIntDesc(C.Structure):
+    """Mirror of `satrans_autoint_desc` (the interacting stack, the DNN, dnn_linear and out.bias of AutoInt's head)."""
+    _fields_ = ([("B", C.c_int32), ("F", C.c_int32), ("D", C.c_int32), ("H", C.c_int32), ("flags", C.c_uint32),
+                 ("n_layers", C.c_int32), ("dense_dim", C.c_int32), ("n_dnn", C.c_int32), ("width", C.c_int32 * MMOE_MAX_HIDDEN),
+                 ("reserved", C.c_int32), ("emb", _vp), ("dense", _vp)] +
+                [(name, _vp * AUTOINT_MAX_LAYERS) for name in INTERACTING_POINTERS] + _AUTOINT_POINTER_FIELDS)
+
+
+class AutoIntGrads(C.Structure):
+    """Mirror of `satrans_autoint_grads`; int_w[l]: layer l's [3 or 4, D, D] block."""
+    _fields_ = [("int_w", _vp * AUTOINT_MAX_LAYERS)] + list(_AUTOINT_POINTER_FIELDS)
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -495,6 +525,14 @@ SIGNATURES = {
     "satrans_fmhead_workspace_floats": (C.c_int64, [C.POINTER(FMHeadDesc)]),
     "satrans_fmhead_fwd": (C.c_int, [C.POINTER(FMHeadDesc), _vp, _vp, _vp]),
     "satrans_fmhead_bwd": (C.c_int, [C.POINTER(FMHeadDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(FMHeadGrads), _vp]),
+    "satrans_interacting_saved_floats": (C.c_int64, [C.POINTER(InteractingDesc)]),
+    "satrans_interacting_scratch_floats": (C.c_int64, [C.POINTER(InteractingDesc)]),
+    "satrans_interacting_fwd": (C.c_int, [C.POINTER(InteractingDesc), _vp, _vp, _vp, _vp]),
+    "satrans_interacting_bwd": (C.c_int, [C.POINTER(InteractingDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "satrans_autoint_saved_floats": (C.c_int64, [C.POINTER(AutoIntDesc)]),
+    "satrans_autoint_workspace_floats": (C.c_int64, [C.POINTER(AutoIntDesc)]),
+    "satrans_autoint_fwd": (C.c_int, [C.POINTER(AutoIntDesc), _vp, C.POINTER(_vp), _vp, _vp]),
+    "satrans_autoint_bwd": (C.c_int, [C.POINTER(AutoIntDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(AutoIntGrads), _vp]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
