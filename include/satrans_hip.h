@@ -46,7 +46,8 @@ extern "C" {
  *    satrans_bilinear_*, satrans_fibinet_*), and PNN's inner and outer product layers and head (satrans_inner_product_*,
  *    satrans_outer_product_*, satrans_pnn_*), and FM, BiInteractionPooling, AFM and the DeepFM / NFM heads (satrans_fm_*,
  *    satrans_bipool_*, satrans_afm_*, satrans_fmhead_*), and AutoInt's interacting layer and head (satrans_interacting_*,
- *    satrans_autoint_*). */
+ *    satrans_autoint_*), and ESMM's two towers and WDL's DNN head with dropout (satrans_esmm_desc, satrans_esmm_grads,
+ *    satrans_esmm_*). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -1091,6 +1092,65 @@ int64_t satrans_autoint_workspace_floats(const satrans_autoint_desc* d);
 int satrans_autoint_fwd(const satrans_autoint_desc* d, float* logit, float* const* att, float* saved, void* stream);
 int satrans_autoint_bwd(const satrans_autoint_desc* d, const float* dlogit, float* demb, float* ddense, const float* saved,
                         float* workspace, const satrans_autoint_grads* g, void* stream);
+
+/* ESMM's two towers (models/esmm.py:84-96) and WDL's DNN-only head (models/wdl.py:75-79), with dropout inside the DNNs.  Also
+ * additive in ABI version 7: new structs and new symbols only.  Nothing is routed: `towers` DNNs of equal widths over all rows,
+ *     h_{t,l} = drop(relu(h_{t,l-1} dnn_w[l][t]^T + dnn_b[l][t])),  h_{t,0} = x,  l = 1 .. n_dnn;   logit_t = h_{t,n_dnn} final_w[t]^T
+ *     towers = 2 (ESMM)   p_t = sigmoid(logit_t + out_bias[0]);  out [B, 2] = (p_0, p_0 p_1)        (ctr, ctcvr: probabilities)
+ *     towers = 1 (WDL)    out [B, 1] = logit_0 + out_bias[0]                                         (a logit)
+ * x [B, C]; dnn_w[l] [towers, n_l, n_{l-1}] (n_0 = C), dnn_b[l] [towers, n_l], final_w [towers, n_last] (no final bias, as in
+ * the reference), out_bias [1].  fp32 throughout, products on the exact f32-input MFMA.  1 to SATRANS_MMOE_MAX_HIDDEN hidden
+ * layers; C and the widths are any positive integers.  Row tiles and weight-gradient chunks are those of the MMoE head.
+ * Layer 1 of both towers is one product of N = towers * n_1, later layers are block-diagonal.  Two forms of the tail, chosen by
+ * satrans_esmm_set_forward (process-wide; returns the previous mode, or SATRANS_E_BADARG), with the same bits in out and saved,
+ * with and without dropout:
+ *     1, the default   composed: the last hidden layer and the final layer are two launches of the tile product (the second
+ *                      with N = 1), then for towers = 2 a pointwise kernel
+ *     0                fused: the last hidden layer, the final layer, the sigmoids and the product are ONE launch (with
+ *                      n_dnn = 1 the whole head): per row the chain logit_t = fmaf(h[n], final_w[t][n], logit_t), n ascending
+ * The fused tail was measured against the composed form and was not faster (profiles/esmm_time.txt), so it is not the default.
+ * Dropout: with SATRANS_TRAIN in flags and drop_p > 0, element (row, n) of tower t's hidden layer l (0-based) is kept iff
+ *     drop_keep(drop_sample_key(drop_site_key(seed, step, l, t), row + row_offset), n, drop_threshold(drop_p))       (csrc/rng.h)
+ * and a kept element is scaled by 1.0f / (1.0f - drop_p); oracle.satrans_oracle.dropout_keep(seed, step, l, t, row + row_offset,
+ * n, p) restates it.  Without SATRANS_TRAIN, or with drop_p = 0, the kernels without the option are launched.  The backward
+ * must see the forward's seed, step, row_offset, flags and drop_p (it reads only the scale: no mask is regenerated - a saved
+ * h > 0 is "kept and past the relu").
+ * saved: the hidden rows, layer by layer [B, towers * n_l] (tower t in columns [t n_l, (t + 1) n_l)), dropped-out and scaled in
+ * training; then, with towers = 2, (p_0, p_1) [B, 2].  The forward needs no workspace; the backward's holds two
+ * [B, widest stacked row] dz buffers and the per-chunk partials of the layer in hand.  From dout [B, towers]:
+ *     dp_0 = dout_0 + dout_1 p_1,  dp_1 = dout_1 p_0,  dlogit_t = dp_t p_t (1 - p_t)          (towers = 1: dlogit_0 = dout)
+ *     dz_t[row, n] = h_t[row, n] > 0 ? dlogit_t final_w[t][n] (* scale) : 0;   d out_bias = sum over rows of (dlogit_0 + dlogit_1)
+ * The backward WRITES dx [B, C] and every gradient of satrans_esmm_grads, each of the shape of its parameter.  No
+ * floating-point atomics: chunks merge in chunk order, so equal inputs give equal bits, and a sample alone gives the bits it
+ * gives inside a batch (its out row and dx row; with dropout when row_offset places it where it sat).  Every size and grid is
+ * decided before a device is touched: SATRANS_E_UNSUPPORTED beyond 2^31 workgroups. */
+typedef struct satrans_esmm_desc {
+    int32_t B, C;
+    int32_t towers;                         /* 1 = WDL, 2 = ESMM */
+    int32_t n_dnn;                          /* hidden layers of a tower */
+    int32_t width[SATRANS_MMOE_MAX_HIDDEN];
+    uint32_t flags;                         /* SATRANS_TRAIN */
+    float drop_p;                           /* 0 <= p < 1 */
+    uint32_t seed, step;
+    uint32_t row_offset;                    /* of row 0 in the global batch, for the masks */
+    const float* x;                         /* [B, C] */
+    const float* dnn_w[SATRANS_MMOE_MAX_HIDDEN];
+    const float* dnn_b[SATRANS_MMOE_MAX_HIDDEN];
+    const float* final_w;
+    const float* out_bias;
+} satrans_esmm_desc;
+typedef struct satrans_esmm_grads {
+    float* dnn_w[SATRANS_MMOE_MAX_HIDDEN];
+    float* dnn_b[SATRANS_MMOE_MAX_HIDDEN];
+    float* final_w;
+    float* out_bias;
+} satrans_esmm_grads;
+int64_t satrans_esmm_saved_floats(const satrans_esmm_desc* d);
+int64_t satrans_esmm_workspace_floats(const satrans_esmm_desc* d);
+int satrans_esmm_fwd(const satrans_esmm_desc* d, float* out, float* saved, void* stream);
+int satrans_esmm_bwd(const satrans_esmm_desc* d, const float* dout, float* dx, const float* saved, float* workspace,
+                     const satrans_esmm_grads* g, void* stream);
+int satrans_esmm_set_forward(int composed);
 
 /* Backward of one layer.  Recomputes the forward from d->x (same dropout counters), so nothing but
  * the layer input is kept between the passes.

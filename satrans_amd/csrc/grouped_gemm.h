@@ -1,8 +1,9 @@
-// The grouped 64 x 64 tile product of the scenario heads (mmoe.hip, ple.hip, sharedbottom.hip, adasparse.hip) and of STAR's
-// towers (star.hip), its weight-gradient and reduce kernels, and the softmax mixture over up to 8 experts.  Every kernel sits
+// The grouped 64 x 64 tile product of the scenario heads (mmoe.hip, ple.hip, sharedbottom.hip, adasparse.hip), of the dense
+// DNNs of the single-task heads (fibinet.hip, pnn.hip, fm.hip, autoint.hip, esmm.hip) and of STAR's towers (star.hip), its weight-gradient and reduce kernels, and the softmax mixture over up to 8 experts.  Every kernel sits
 // in an unnamed namespace: each file that includes this header gets its own copies, under the names mmoe.hip gave them.
 // star.hip wraps the same tile body with the shared factor switched on (SHARED: W_dom * W_sh on operand load, b_dom + b_sh)
-// and the weight-gradient body with G = 1 as a constant.  This header is device code only; the host code that launches it for
+// and the weight-gradient body with G = 1 as a constant; esmm.hip switches on the dropout option of the dense form (DROP,
+// mmoe_gemm_drop_kernel).  This header is device code only; the host code that launches it for
 // the four heads (a layer, a batch, launch_fwd / launch_bwd, the grid check, the walks over a DNN) is head_layers.h.
 //
 // Layout.  Rows, hidden rows, dz and dx stay in the caller's row order.  The hidden rows of G blocks of a layer sit side by
@@ -18,6 +19,8 @@
 // next step's global loads are issued before the current step's MFMAs.
 #pragma once
 #include "seg_walk.h"
+// (after seg_walk.h, which brings in the HIP runtime)
+#include "rng.h"
 
 namespace satrans {
 namespace {
@@ -67,18 +70,40 @@ __device__ __forceinline__ int unit_row(const int32_t* __restrict__ order, int p
 
 // ---- forward layers and the input gradients -------------------------------------------------------------------------------------
 
+// The dropout option of a hidden layer (DROP; off by default, and then nothing of it is compiled in).  The keep bit is rng.h's
+// counter-based function of (seed, step, layer, site, row + row_offset, column), so it depends neither on the tiling nor on what
+// else is in the batch; oracle.satrans_oracle.dropout_keep restates it.  A layer whose output stacks several sites side by
+// side (a first layer shared by two towers) gives `per`, the columns of one site: column n of block g belongs to site
+// site + g + n / per and is element n % per of it.  Forward: h = keep ? relu(z) * scale : 0.  Backward: nothing is regenerated -
+// h > 0 already means "kept and past the relu" - and the masked input gradient becomes mask > 0 ? v * scale : 0.
+struct DropArgs {
+    uint32_t seed, step;
+    int layer, site, per;      // per = 0: the whole block is one site
+    uint32_t thresh;           // drop_threshold(p)
+    float scale;               // 1 / (1 - p), formed on the host
+    uint32_t row_offset;       // of the caller's row 0 in the global batch
+};
+
+// the site key and the element index of output column n of block blk
+__device__ __forceinline__ uint32_t drop_column(const DropArgs& dr, int blk, int n, uint32_t& elem) {
+    const int s = dr.per > 0 ? n / dr.per : 0;
+    elem = (uint32_t)(dr.per > 0 ? n - s * dr.per : n);
+    return drop_site_key(dr.seed, dr.step, dr.layer, dr.site + blk + s);
+}
+
 // group of the workgroup: block g of G (dense) or block g of G of the rows' task t (ROUTED; G = 1: the task's whole rows).
 // W = w + g N K (dense) or w + (t G + g) N K (ROUTED), times w_sh [N, K] elementwise when SHARED; row strides ldin / ldout:
 //   out[row, g ogo + n] = epilogue(sum_k in[row, g igo + k] * W[n, k])            WT = false   (W [N, K])
 //   out[row, g ogo + n] = epilogue(sum_k in[row, g igo + k] * W[k, n])            WT = true    (W [K, N])
 // epilogue: + bias[group N + n] (+ b_sh[n] when SHARED) (when bias), relu (when relu), * (mask[same place as out] > 0) (when
-// mask), + out (when add)
-template <bool WT, bool ROUTED, bool SHARED>
+// mask), + out (when add).  DROP: the forward epilogue (WT = false) drops after the relu, the masked one (WT = true) scales.
+template <bool WT, bool ROUTED, bool SHARED, bool DROP = false>
 __device__ __forceinline__ void gemm_tile(const float* __restrict__ in, int ldin, int igo, const int32_t* __restrict__ order,
                                           const int32_t* __restrict__ seg, int B, int K, int N, int S, int G, int ntiles,
                                           const float* __restrict__ w, const float* __restrict__ w_sh,
                                           const float* __restrict__ bias, const float* __restrict__ b_sh, int relu,
-                                          const float* __restrict__ mask, int add, float* out, int ldout, int ogo) {
+                                          const float* __restrict__ mask, int add, float* out, int ldout, int ogo,
+                                          const DropArgs& dr = DropArgs{}) {
     __shared__ float As[kTM][kLd];
     __shared__ float Bs[kTN][kLd];
     __shared__ int rows_sh[kTM];
@@ -142,14 +167,19 @@ __device__ __forceinline__ void gemm_tile(const float* __restrict__ in, int ldin
     const int n = n0 + wn * 32 + (lane & 31);
     if (n >= N) return;
     const float bv = bias ? (SHARED ? bias[grp * N + n] + b_sh[n] : bias[grp * N + n]) : 0.f;
+    uint32_t site_key = 0, elem = 0;
+    if (DROP && !WT) site_key = drop_column(dr, blk, n, elem);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         const int row = rows_sh[wm * 32 + (q & 3) + 8 * (q >> 2) + 4 * (lane >> 5)];
         if (row < 0) continue;
         float v = acc[q] + bv;
         if (relu) v = fmaxf(v, 0.f);
+        if (DROP && !WT) v = drop_keep(drop_sample_key(site_key, (uint32_t)row + dr.row_offset), elem, dr.thresh) ? v * dr.scale : 0.f;
         const size_t at = (size_t)row * ldout + oc + n;
-        if (mask) v = mask[at] > 0.f ? v : 0.f;
+        if (DROP && WT) {
+            if (mask) v = mask[at] > 0.f ? v * dr.scale : 0.f;
+        } else if (mask) v = mask[at] > 0.f ? v : 0.f;
         if (add) v = out[at] + v;
         out[at] = v;
     }
@@ -165,6 +195,17 @@ __global__ __launch_bounds__(kThreads) void mmoe_gemm_kernel(const float* __rest
                                                              int ogo) {
     gemm_tile<WT, ROUTED, false>(in, ldin, igo, order, seg, B, K, N, S, G, ntiles, w, nullptr, bias, nullptr, relu, mask, add, out,
                                  ldout, ogo);
+}
+
+// the same launch with the dropout option on; dense only (the routed heads refuse dropout)
+template <bool WT>
+__global__ __launch_bounds__(kThreads) void mmoe_gemm_drop_kernel(const float* __restrict__ in, int ldin, int igo, int B, int K, int N,
+                                                                  int G, int ntiles, const float* __restrict__ w,
+                                                                  const float* __restrict__ bias, int relu,
+                                                                  const float* __restrict__ mask, int add, float* out, int ldout,
+                                                                  int ogo, DropArgs dr) {
+    gemm_tile<WT, false, false, true>(in, ldin, igo, nullptr, nullptr, B, K, N, 0, G, ntiles, w, nullptr, bias, nullptr, relu, mask,
+                                      add, out, ldout, ogo, dr);
 }
 
 // ---- softmax and mixture --------------------------------------------------------------------------------------------------------

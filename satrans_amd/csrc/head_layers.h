@@ -1,6 +1,7 @@
 // The host side of grouped_gemm.h for the scenario heads (mmoe.hip, ple.hip, sharedbottom.hip, adasparse.hip): what a layer and
 // a batch look like to a launch, the three launches of a layer's forward and backward, the per-layer grid check, and the walks
-// over a DNN and over the dense block-diagonal expert stack.  It sits in the same unnamed namespace as the kernels, so every
+// over a DNN and over the dense block-diagonal expert stack, each with the dropout option of the dense launches as a template
+// argument that defaults off (esmm.hip is its one user so far).  It sits in the same unnamed namespace as the kernels, so every
 // file still launches its own kernel copies.  star.hip keeps its own launches (the SHARED wrappers, a reduce of its own) and
 // does not include this header.
 #pragma once
@@ -44,12 +45,20 @@ inline int64_t layer_part(const Rows& r, bool routed, const Lyr& y, const char* 
 }
 
 // out[:, block * ogo + n] = epilogue(in[:, block * igo + k] W^T) of one layer; in / out are rows of ldin / ldout floats; `add`:
-// added to what out holds
-template <bool ROUTED>
+// added to what out holds.  DROP (dense layers only; grouped_gemm.h's DropArgs, with layer, site and per set for this layer): the
+// hidden layer's dropout in its epilogue.
+template <bool ROUTED, bool DROP = false>
 int launch_fwd(const Rows& r, const Lyr& y, const float* in, int ldin, int igo, int relu, float* out, int ldout, int ogo,
-               hipStream_t st, int add = 0) {
+               hipStream_t st, int add = 0, const DropArgs& dr = DropArgs{}) {
+    static_assert(!(ROUTED && DROP), "dropout is built for the dense launches");
     const int ntiles = (int)ceil_div(y.N, kTN);
     const int64_t units = (ROUTED ? r.slots : r.tiles) * y.G;
+    if constexpr (DROP) {
+        mmoe_gemm_drop_kernel<false><<<(unsigned)(units * ntiles), kThreads, 0, st>>>(in, ldin, igo, r.B, y.K, y.N, y.G, ntiles, y.w, y.b,
+                                                                                      relu, nullptr, add, out, ldout, ogo, dr);
+        SATRANS_CHECK_LAUNCH("mmoe_gemm_drop_kernel (forward)");
+        return SATRANS_OK;
+    }
     mmoe_gemm_kernel<false, ROUTED><<<(unsigned)(units * ntiles), kThreads, 0, st>>>(in, ldin, igo, r.order, r.seg, r.B, y.K, y.N, r.T, y.G,
                                                                                      ntiles, y.w, y.b, relu, nullptr, add, out, ldout, ogo);
     SATRANS_CHECK_LAUNCH("mmoe_gemm_kernel (forward)");
@@ -58,10 +67,12 @@ int launch_fwd(const Rows& r, const Lyr& y, const float* in, int ldin, int igo, 
 
 // the backward of one layer: its parameter gradients from (dz, hin) through `part`, the start of the partials region, then
 // din = dz W, masked by hin > 0 (when masked), added to what din holds (when add).  dz rows of ldz floats with block offset
-// y.N; hin / din rows of ldh floats with block offset hgo.
-template <bool ROUTED>
+// y.N; hin / din rows of ldh floats with block offset hgo.  DROP: hin went through dropout, so the masked din is also scaled
+// (dr.scale; nothing else of dr is read).
+template <bool ROUTED, bool DROP = false>
 int launch_bwd(const Rows& r, const Lyr& y, const float* dz, int ldz, const float* hin, int ldh, int hgo, bool masked, int add,
-               float* din, float* part, hipStream_t st) {
+               float* din, float* part, hipStream_t st, const DropArgs& dr = DropArgs{}) {
+    static_assert(!(ROUTED && DROP), "dropout is built for the dense launches");
     const int64_t NK = (int64_t)y.N * y.K;
     const int ntiles = (int)ceil_div(y.N, kTM), ktiles = (int)ceil_div(y.K, kTN);
     const int64_t units = (ROUTED ? r.dw_slots : r.chunks) * y.G;
@@ -77,6 +88,12 @@ int launch_bwd(const Rows& r, const Lyr& y, const float* dz, int ldz, const floa
     SATRANS_CHECK_LAUNCH("mmoe_reduce_kernel");
     const int otiles = (int)ceil_div(y.K, kTN);      // contraction over this layer's N outputs, K columns out
     const int64_t gunits = (ROUTED ? r.slots : r.tiles) * y.G;
+    if constexpr (DROP) {
+        mmoe_gemm_drop_kernel<true><<<(unsigned)(gunits * otiles), kThreads, 0, st>>>(dz, ldz, y.N, r.B, y.N, y.K, y.G, otiles, y.w, nullptr, 0,
+                                                                                      masked ? hin : nullptr, add, din, ldh, hgo, dr);
+        SATRANS_CHECK_LAUNCH("mmoe_gemm_drop_kernel (backward)");
+        return SATRANS_OK;
+    }
     mmoe_gemm_kernel<true, ROUTED><<<(unsigned)(gunits * otiles), kThreads, 0, st>>>(dz, ldz, y.N, r.order, r.seg, r.B, y.N, y.K, r.T, y.G,
                                                                                     otiles, y.w, nullptr, 0, masked ? hin : nullptr, add,
                                                                                     din, ldh, hgo);
@@ -144,13 +161,17 @@ inline void set_grads(Chain& c, float* const* w, float* const* b, float* final_w
 }
 
 // a gate or tower DNN and its final layer, forward: hidden rows into saved, the final layer's output into `out` (`add`: added
-// to what `out` holds)
-template <bool ROUTED>
-int dnn_fwd(const Rows& r, const Chain& c, const float* in, float* saved, float* out, hipStream_t st, int add = 0) {
+// to what `out` holds).  DROP: every hidden layer l drops with (dr.seed, dr.step, layer l, dr.site); the final layer does not.
+template <bool ROUTED, bool DROP = false>
+int dnn_fwd(const Rows& r, const Chain& c, const float* in, float* saved, float* out, hipStream_t st, int add = 0,
+            DropArgs dr = DropArgs{}) {
     for (int l = 0; l < c.n; ++l) {
         const bool fin = l == c.n - 1;
         float* o = fin ? out : saved + c.s[l];
-        if (int rc = launch_fwd<ROUTED>(r, c.y[l], in, c.y[l].K, 0, fin ? 0 : 1, o, c.y[l].N, 0, st, fin ? add : 0)) return rc;
+        dr.layer = l, dr.per = 0;
+        const int rc = DROP && !fin ? launch_fwd<ROUTED, DROP>(r, c.y[l], in, c.y[l].K, 0, 1, o, c.y[l].N, 0, st, 0, dr)
+                                    : launch_fwd<ROUTED>(r, c.y[l], in, c.y[l].K, 0, fin ? 0 : 1, o, c.y[l].N, 0, st, fin ? add : 0);
+        if (rc) return rc;
         in = o;
     }
     return SATRANS_OK;
@@ -158,14 +179,15 @@ int dnn_fwd(const Rows& r, const Chain& c, const float* in, float* saved, float*
 
 // the backward of a DNN from dz of its last layer, alternating the two dz buffers (cur: the one the next product writes).  The
 // first layer's input gradient goes to din (written, or added when add); a null din: to buf[cur], which then counts as written.
-template <bool ROUTED>
+// DROP: the saved hidden rows went through dropout (dr.scale).
+template <bool ROUTED, bool DROP = false>
 int dnn_bwd(const Rows& r, const Chain& c, const float* dz, const float* in, const float* saved, int add, float* din, float* buf[2],
-            int& cur, float* part, hipStream_t st) {
+            int& cur, float* part, hipStream_t st, const DropArgs& dr = DropArgs{}) {
     for (int l = c.n - 1; l >= 0; --l) {
         const Lyr& y = c.y[l];
         const bool first = l == 0;
         float* o = first && din ? din : buf[cur];
-        if (int rc = launch_bwd<ROUTED>(r, y, dz, y.N, first ? in : saved + c.s[l - 1], y.K, 0, !first, first ? add : 0, o, part, st))
+        if (int rc = launch_bwd<ROUTED, DROP>(r, y, dz, y.N, first ? in : saved + c.s[l - 1], y.K, 0, !first, first ? add : 0, o, part, st, dr))
             return rc;
         if (o != din) cur ^= 1;
         dz = o;
@@ -173,24 +195,30 @@ int dnn_bwd(const Rows& r, const Chain& c, const float* dz, const float* in, con
     return SATRANS_OK;
 }
 
-// the dense block-diagonal expert stack over in [B, ldin]: hidden rows [B, G N] into saved, the last of them the experts' output
-inline int experts_fwd(const Rows& r, const Chain& c, const float* in, int ldin, float* saved, hipStream_t st) {
-    for (int l = 0; l < c.n; ++l) {
+// the dense block-diagonal expert stack over in [B, ldin]: hidden rows [B, G N] into saved, the last of them the experts' output.
+// The layers [0, n) of the chain (n < 0: all).  DROP: block g is site dr.site + g; `blocks` cuts the first layer's one product.
+template <bool DROP = false>
+int experts_fwd(const Rows& r, const Chain& c, const float* in, int ldin, float* saved, hipStream_t st, int n = -1, int blocks = 1,
+                DropArgs dr = DropArgs{}) {
+    for (int l = 0; l < (n < 0 ? c.n : n); ++l) {
         const Lyr& y = c.y[l];
         float* out = saved + c.s[l];
-        if (int rc = launch_fwd<false>(r, y, in, ldin, l == 0 ? 0 : y.K, 1, out, y.N * y.G, y.N, st)) return rc;
+        dr.layer = l, dr.per = l == 0 ? y.N / blocks : 0;
+        if (int rc = launch_fwd<false, DROP>(r, y, in, ldin, l == 0 ? 0 : y.K, 1, out, y.N * y.G, y.N, st, 0, dr)) return rc;
         in = out;
         ldin = y.N * y.G;
     }
     return SATRANS_OK;
 }
 
-// its backward from dz of the last layer; the first layer WRITES din [B, ldin]
-inline int experts_bwd(const Rows& r, const Chain& c, const float* dz, const float* in, int ldin, const float* saved, float* din,
-                       float* buf[2], int& cur, float* part, hipStream_t st) {
+// its backward from dz of the last layer; the first layer WRITES din [B, ldin].  DROP: the saved rows went through dropout.
+template <bool DROP = false>
+int experts_bwd(const Rows& r, const Chain& c, const float* dz, const float* in, int ldin, const float* saved, float* din,
+                float* buf[2], int& cur, float* part, hipStream_t st, const DropArgs& dr = DropArgs{}) {
     for (int l = c.n - 1; l > 0; --l) {
         const Lyr& y = c.y[l];
-        if (int rc = launch_bwd<false>(r, y, dz, y.N * y.G, saved + c.s[l - 1], y.K * y.G, y.K, true, 0, buf[cur], part, st)) return rc;
+        if (int rc = launch_bwd<false, DROP>(r, y, dz, y.N * y.G, saved + c.s[l - 1], y.K * y.G, y.K, true, 0, buf[cur], part, st, dr))
+            return rc;
         dz = buf[cur];
         cur ^= 1;
     }

@@ -57,9 +57,13 @@
     `AutoIntHead`, the part of AutoInt.forward behind the embeddings (autoint.py:93-121), the whole head one autograd.Function
     (csrc/autoint.hip).
 
+  * `ESMMHead` - the two towers, sigmoids and product of the reference's ESMM.forward (models/esmm.py:84-96), and `WDLHead`, the
+    DNN half of WDL.forward (models/wdl.py:75-77): the same kernels at two towers and at one, with dropout inside the DNNs as a
+    compile-time option of the dense layer launcher of csrc/head_layers.h, each head one autograd.Function (csrc/esmm.hip).
+
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
 csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip, csrc/fibinet.hip, csrc/pnn.hip, csrc/fm.hip,
-csrc/autoint.hip) wrapped
+csrc/autoint.hip, csrc/esmm.hip) wrapped
 in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
@@ -2847,4 +2851,191 @@ class AutoIntHead(nn.Module):
         for layer, att, on in zip(self.int_layers, atts, capture):
             if on:
                 layer.normalized_att_scores = att
+        return logit
+
+
+def _esmm_fill(tgt, n_dnn, tensors):
+    """Set the parameter pointers of a satrans_esmm_desc / satrans_esmm_grads from `tensors`: the layers' weights [towers, n_l,
+    n_{l-1}], their biases [towers, n_l], the final weights [towers, n_last], out.bias [1]."""
+    for l in range(n_dnn):
+        tgt.dnn_w[l], tgt.dnn_b[l] = tensors[l].data_ptr(), tensors[n_dnn + l].data_ptr()
+    tgt.final_w, tgt.out_bias = tensors[-2].data_ptr(), tensors[-1].data_ptr()
+    return tgt
+
+
+def _esmm_desc(x, cfg, tensors):
+    """cfg = (towers, training, drop_p, seed, step, row_offset): what the backward must see as the forward saw it."""
+    towers, training, drop_p, seed, step, row_offset = cfg
+    n_dnn = (len(tensors) - 2) // 2
+    d = _esmm_fill(N.ESMMDesc(), n_dnn, tensors)
+    d.B, d.C, d.towers, d.n_dnn = x.shape[0], x.shape[1], towers, n_dnn
+    for l in range(n_dnn):
+        d.width[l] = tensors[n_dnn + l].shape[-1]
+    d.flags, d.drop_p = (N.TRAIN if training else 0), drop_p
+    d.seed, d.step, d.row_offset = seed, step, row_offset
+    d.x = x.data_ptr()
+    return d
+
+
+class _ESMMFn(torch.autograd.Function):
+    """out [B, towers] of ESMM's two towers (towers = 2: the probabilities ctr, ctcvr) or of WDL's DNN head (towers = 1: the
+    logit) (csrc/esmm.hip); cfg as _esmm_desc takes it, `tensors` as _esmm_fill lists them.  `saved` = the hidden rows, then
+    with two towers (p_ctr, p_cvr) [B, 2]."""
+
+    @staticmethod
+    def forward(ctx, x, cfg, *tensors):
+        lib = N.lib()
+        dev = x.device
+        x = x.contiguous()
+        tensors = tuple(t.contiguous() for t in tensors)
+        d = _esmm_desc(x, cfg, tensors)
+        saved = torch.empty(_native_size(lib.satrans_esmm_saved_floats, d), dtype=torch.float32, device=dev)
+        out = torch.empty(x.shape[0], cfg[0], dtype=torch.float32, device=dev)
+        N.check(lib.satrans_esmm_fwd(C.byref(d), out.data_ptr(), saved.data_ptr(), N.stream_handle(dev)), "satrans_esmm_fwd")
+        ctx.cfg = cfg      # carries the forward's step into the backward
+        ctx.save_for_backward(x, saved, *tensors)
+        ctx.mark_non_differentiable(saved)
+        return out, saved
+
+    @staticmethod
+    def backward(ctx, dout, _dsaved):
+        lib = N.lib()
+        x, saved, *tensors = ctx.saved_tensors
+        d = _esmm_desc(x, ctx.cfg, tensors)
+        work = torch.empty(_native_size(lib.satrans_esmm_workspace_floats, d), dtype=torch.float32, device=x.device)
+        dx = torch.empty_like(x)
+        grads = [torch.empty_like(t) for t in tensors]
+        g = _esmm_fill(N.ESMMGrads(), d.n_dnn, grads)
+        N.check(lib.satrans_esmm_bwd(C.byref(d), dout.contiguous().data_ptr(), dx.data_ptr(), saved.data_ptr(), work.data_ptr(),
+                                     C.byref(g), N.stream_handle(x.device)), "satrans_esmm_bwd")
+        return (dx, None, *grads)
+
+
+class _DropoutDNNHead(nn.Module):
+    """What ESMMHead and WDLHead share: the checks of the constructor and of a call, the dropout clock, the call of _ESMMFn."""
+
+    def _init_common(self, what, inputs_dim, hidden_units, l2_reg_dnn, dnn_dropout, dnn_activation, dnn_use_bn):
+        if dnn_activation != 'relu':
+            raise NotImplementedError(f"{what}: activation {dnn_activation!r} is not built (relu only)")
+        if dnn_use_bn:
+            raise NotImplementedError(f"{what}: batch-norm inside the DNNs is not built (dnn_use_bn must be False)")
+        units = [int(u) for u in hidden_units]
+        if len(units) == 0:
+            raise ValueError(f"{what}: the hidden units are empty (the reference has no such head)")
+        if len(units) > N.MMOE_MAX_HIDDEN:
+            raise NotImplementedError(f"{what}: up to MMOE_MAX_HIDDEN = {N.MMOE_MAX_HIDDEN} hidden layers, got {len(units)}")
+        if inputs_dim < 1 or min(units) < 1:
+            raise ValueError(f"{what}: inputs_dim and the hidden units must be positive")
+        if not 0 <= dnn_dropout < 1:
+            raise ValueError(f"{what}: dnn_dropout must lie in [0, 1), got {dnn_dropout}")
+        self.inputs_dim, self.l2_reg_dnn, self.dnn_dropout = int(inputs_dim), float(l2_reg_dnn), float(dnn_dropout)
+        self.drop_row_offset = 0
+        self._clock = _DropClock()
+        self._units, self.last_hidden = tuple(units), None
+        return units
+
+    def _l2(self, weights):
+        total = torch.zeros((1,), device=self.out.bias.device)
+        if self.l2_reg_dnn > 0:
+            for p in weights:
+                total = total + torch.sum(self.l2_reg_dnn * torch.square(p))
+        return total
+
+    def _run(self, what, towers, x, tensors):
+        if x.dim() != 2 or x.shape[1] != self.inputs_dim:
+            raise ValueError(f"{what}: expected input [B, {self.inputs_dim}], got {tuple(x.shape)}")
+        N.require_gpu(x, what)
+        if x.dtype != torch.float32 or self.out.bias.dtype != torch.float32:
+            raise TypeError(f"{what}: rows, parameters and gradients are float32")
+        if self.training:
+            self._clock.step += 1
+        cfg = (towers, bool(self.training), self.dnn_dropout, self._clock.seed, self._clock.step & 0xFFFFFFFF,
+               int(self.drop_row_offset) & 0xFFFFFFFF)
+        out, saved = _ESMMFn.apply(x, cfg, *tensors)
+        B, at, self.last_hidden = x.shape[0], 0, []
+        for n in self._units:      # views of the saved buffer: layer l's rows [B, towers * n_l], tower t in columns [t n_l, (t + 1) n_l)
+            self.last_hidden.append(saved[at:at + B * towers * n].view(B, towers * n))
+            at += B * towers * n
+        return out, saved
+
+
+class ESMMHead(_DropoutDNNHead):
+    """The half of the reference's ESMM.forward behind the embedding lookup (models/esmm.py:84-96), sigmoids and product included:
+
+        p_ctr = sigmoid(ctr_dnn_final_layer(ctr_dnn(x)) + out.bias),  p_cvr = sigmoid(cvr_dnn_final_layer(cvr_dnn(x)) + out.bias)
+        forward(dnn_input [B, inputs_dim] fp32) -> [B, 2] = (p_ctr, p_ctr * p_cvr)                          (ctr, ctcvr)
+
+    Probabilities, not logits: ctcvr has none.  `last_cvr` [B, 1] is the detached pCVR of the last forward, `last_hidden[l]`
+    [B, 2 n_l] the hidden rows it saved (ctr_dnn's columns, then cvr_dnn's; dropped-out and scaled in training).  Two towers over all
+    rows, nothing routed; the backward crosses from the product into both towers.  The whole head is ONE autograd.Function over
+    satrans_esmm_fwd / satrans_esmm_bwd (csrc/esmm.hip): layer 1 of both towers one product, later layers block-diagonal, the
+    final layers one product of one column per tower, then the sigmoids and the product.  Per call the two towers' parameters are stacked
+    (torch.stack; autograd splits the gradients back).
+
+    dnn_dropout: in training mode a hidden element is kept iff oracle.satrans_oracle.dropout_keep(seed, step, layer, tower, row +
+    drop_row_offset, column, p) (csrc/rng.h; tower 0 = ctr_dnn, 1 = cvr_dnn) and scaled by 1 / (1 - p); the step advances with
+    every training forward, and the backward sees the forward's.  Not torch's generator stream.  `drop_row_offset` (default 0)
+    lets a rank or a slice keep the masks of the global batch.  eval() runs the kernels without the option.
+
+    Parameter names, state_dict order and initialisation are the reference ESMM's: out.bias (zeros), ctr_dnn.linears.{l}.*,
+    cvr_dnn.linears.{l}.* (weights N(0, init_std)), ctr_dnn_final_layer.weight, cvr_dnn_final_layer.weight - those entries of a
+    reference checkpoint load with load_state_dict.  regularization_loss() -> [1] is what ESMM.__init__ registers (esmm.py:71-76).
+    Not built: batch-norm and activations other than relu (NotImplementedError), more than MMOE_MAX_HIDDEN hidden layers, bf16,
+    an ESMM model class behind BaseModel.  Empty hidden units: ValueError (the reference indexes [-1])."""
+
+    def __init__(self, inputs_dim, tower_dnn_hidden_units=(256, 128), l2_reg_dnn=0, init_std=0.0001, dnn_dropout=0,
+                 dnn_activation='relu', dnn_use_bn=False):
+        super().__init__()
+        units = self._init_common("ESMMHead", inputs_dim, tower_dnn_hidden_units, l2_reg_dnn, dnn_dropout, dnn_activation, dnn_use_bn)
+        self.tower_dnn_hidden_units = tuple(units)
+        # (first: in the reference's state_dict `out.*` precedes ESMM's own modules, because its BaseModel registers that name)
+        self.out = _OutBias()
+        self.ctr_dnn = _TowerDNN(inputs_dim, units, init_std)
+        self.cvr_dnn = _TowerDNN(inputs_dim, units, init_std)
+        self.ctr_dnn_final_layer = nn.Linear(units[-1], 1, bias=False)
+        self.cvr_dnn_final_layer = nn.Linear(units[-1], 1, bias=False)
+        self.last_cvr = None
+
+    def regularization_loss(self):
+        return self._l2([lin.weight for lin in self.ctr_dnn.linears] + [lin.weight for lin in self.cvr_dnn.linears] +
+                        [self.ctr_dnn_final_layer.weight, self.cvr_dnn_final_layer.weight])
+
+    def forward(self, dnn_input):
+        pairs = list(zip(self.ctr_dnn.linears, self.cvr_dnn.linears))
+        tensors = ([torch.stack([a.weight, b.weight]) for a, b in pairs] + [torch.stack([a.bias, b.bias]) for a, b in pairs] +
+                   [torch.cat([self.ctr_dnn_final_layer.weight, self.cvr_dnn_final_layer.weight]), self.out.bias])
+        out, saved = self._run("ESMMHead", 2, dnn_input, tensors)
+        B = out.shape[0]
+        self.last_cvr = saved[saved.numel() - 2 * B:].view(B, 2)[:, 1:2]
+        return out
+
+
+class WDLHead(_DropoutDNNHead):
+    """The DNN half of the reference's WDL.forward (models/wdl.py:75-77) with the bias of `self.out`:
+
+        forward(dnn_input [B, inputs_dim] fp32) -> logit [B, 1] = dnn_linear(dnn(x)) + out.bias;  the caller keeps the sigmoid
+
+    (wdl.py leaves linear_model out of the logit.)  ESMM's tower taken once: the same kernels at one tower (csrc/esmm.hip), ONE
+    autograd.Function.  dnn_dropout, `drop_row_offset`, training / eval as in ESMMHead, with site 0 for `dnn`.  Parameter names,
+    state_dict order and initialisation are the reference WDL's head entries: out.bias, dnn.linears.{l}.{weight,bias},
+    dnn_linear.weight.  regularization_loss() -> [1] follows wdl.py:59-61.
+    Not built: batch-norm and activations other than relu (NotImplementedError), more than MMOE_MAX_HIDDEN hidden layers, bf16, a
+    WDL model class behind BaseModel.  Empty hidden units: ValueError (the reference's WDL has no DNN then)."""
+
+    def __init__(self, inputs_dim, dnn_hidden_units=(256, 128), l2_reg_dnn=0, init_std=0.0001, dnn_dropout=0, dnn_activation='relu',
+                 dnn_use_bn=False):
+        super().__init__()
+        units = self._init_common("WDLHead", inputs_dim, dnn_hidden_units, l2_reg_dnn, dnn_dropout, dnn_activation, dnn_use_bn)
+        self.dnn_hidden_units = tuple(units)
+        self.out = _OutBias()
+        self.dnn = _TowerDNN(inputs_dim, units, init_std)
+        self.dnn_linear = nn.Linear(units[-1], 1, bias=False)
+
+    def regularization_loss(self):
+        return self._l2([lin.weight for lin in self.dnn.linears] + [self.dnn_linear.weight])
+
+    def forward(self, dnn_input):
+        tensors = ([lin.weight for lin in self.dnn.linears] + [lin.bias for lin in self.dnn.linears] +
+                   [self.dnn_linear.weight, self.out.bias])
+        logit, _ = self._run("WDLHead", 1, dnn_input, tensors)
         return logit

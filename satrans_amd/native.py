@@ -373,6 +373,24 @@ class AutoIntGrads(C.Structure):
     _fields_ = [("int_w", _vp * AUTOINT_MAX_LAYERS)] + list(_AUTOINT_POINTER_FIELDS)
 
 
+# the parameter pointers of satrans_esmm_desc / satrans_esmm_grads in the header's order: (name, per hidden layer)
+ESMM_POINTERS = (("dnn_w", True), ("dnn_b", True), ("final_w", False), ("out_bias", False))
+_ESMM_POINTER_FIELDS = [(name, _vp * MMOE_MAX_HIDDEN if per_layer else _vp) for name, per_layer in ESMM_POINTERS]
+
+
+class ESMMDesc(C.Structure):
+    """Mirror of `satrans_esmm_desc` (ESMM's two towers, towers = 2, and WDL's DNN head, towers = 1; the layer limit is
+    MMOE_MAX_HIDDEN; flags: TRAIN)."""
+    _fields_ = [("B", C.c_int32), ("C", C.c_int32), ("towers", C.c_int32), ("n_dnn", C.c_int32),
+                ("width", C.c_int32 * MMOE_MAX_HIDDEN), ("flags", C.c_uint32), ("drop_p", C.c_float), ("seed", C.c_uint32),
+                ("step", C.c_uint32), ("row_offset", C.c_uint32), ("x", _vp)] + _ESMM_POINTER_FIELDS
+
+
+class ESMMGrads(C.Structure):
+    """Mirror of `satrans_esmm_grads`."""
+    _fields_ = list(_ESMM_POINTER_FIELDS)
+
+
 class PoolField(C.Structure):
     """Mirror of `satrans_pool_field` (one field of the pooled gather; passed as a host array)."""
     _fields_ = [("col", C.c_int32), ("maxlen", C.c_int32), ("combiner", C.c_int32), ("len_col", C.c_int32),
@@ -533,6 +551,11 @@ SIGNATURES = {
     "satrans_autoint_workspace_floats": (C.c_int64, [C.POINTER(AutoIntDesc)]),
     "satrans_autoint_fwd": (C.c_int, [C.POINTER(AutoIntDesc), _vp, C.POINTER(_vp), _vp, _vp]),
     "satrans_autoint_bwd": (C.c_int, [C.POINTER(AutoIntDesc), _vp, _vp, _vp, _vp, _vp, C.POINTER(AutoIntGrads), _vp]),
+    "satrans_esmm_saved_floats": (C.c_int64, [C.POINTER(ESMMDesc)]),
+    "satrans_esmm_workspace_floats": (C.c_int64, [C.POINTER(ESMMDesc)]),
+    "satrans_esmm_fwd": (C.c_int, [C.POINTER(ESMMDesc), _vp, _vp, _vp]),
+    "satrans_esmm_bwd": (C.c_int, [C.POINTER(ESMMDesc), _vp, _vp, _vp, _vp, C.POINTER(ESMMGrads), _vp]),
+    "satrans_esmm_set_forward": (C.c_int, [C.c_int]),
     "satrans_layer_bwd_slab_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_layer_attn_save_floats": (C.c_int64, [C.POINTER(LayerDesc)]),
     "satrans_batch_metrics": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
