@@ -180,6 +180,67 @@ int satrans_pool_gather_fwd(const float* arena, int64_t arena_rows, const float*
 int satrans_pool_bwd(const float* dx, const satrans_pool_field* fields, int F, int R, int Fv, int B, int D,
                      const uint32_t* mask, const uint8_t* argmax, float* gemb, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * The order-1 ("linear") term of deepctr's models: Linear.forward (reference models/meta_basemodel.py:63-92), the sum of 1-wide
+ * embeddings of the sparse and (pooled) varlen fields plus dense @ weight, and its backward.  Added under ABI 7: new entry
+ * points and a new struct type only.
+ *   arena       [arena_rows] fp32: all 1-wide tables back to back
+ *   fields      HOST array of F satrans_pool_field exactly as satrans_pool_gather_fwd takes it (sparse fields first, then the
+ *               varlen ones; lo / hi are rows of the 1-wide arena; the same limits SATRANS_POOL_MAX_FIELDS / _MAX_LEN); F = 0
+ *               (fields ignored, R = Fv = 0) leaves the dense term alone
+ *   X, id_dtype, x_stride, B   as for the gather
+ *   dense       the fp32 matrix the dense values are read from, rows dense_stride apart: X itself when X is fp32, the dense
+ *               half of a packed input when the ids are integers
+ *   dense_cols  [n_dense] int32 on the DEVICE: the column of `dense` of every dense value in concatenation order (a DenseFeat
+ *               of dimension k is k columns); weight [n_dense]; both NULL with n_dense = 0.  A column outside
+ *               [0, dense_stride) sets bit 1 of *status and reads as 0 (device values cannot be checked on the host).
+ * F = 0 with n_dense = 0 is SATRANS_E_BADARG (nothing to compute: the caller returns zeros).
+ *
+ * satrans_linear_fwd:  logit[b] = sum_f pooled_f(b) + sum_k dense[b, dense_cols[k]] * weight[k]  in fp32 in THIS order: from
+ * 0.0f the fields in descriptor order (the reference's sparse_embedding_list += varlen_embedding_list) by plain additions, then
+ * k ascending by fmaf.  pooled_f follows the pooled gather's rules over 1-wide values: COPY w[row]; SUM over the valid slots in
+ * slot order; MEAN that sum / (count + 1e-8f), a true division, an empty list 0; MAX the max over slots of w - (1 - mask) *
+ * 1e9f, the first maximal slot winning; mask = s < X[b, len_col], or id != 0 with len_col < 0.  An id outside its table sets bit
+ * 0 of *status, reads as 0 and is recorded as row lo.  A sample's logit does not depend on the batch around it: (sample,
+ * field) items are spread over the lanes of a workgroup (SATRANS_LINEAR_SAMPLES samples per workgroup and trip, at most
+ * SATRANS_LINEAR_MAX_BLOCKS workgroups, grid-strided beyond), the pooled values meet in LDS and one lane per sample adds them.
+ *   logit [B, 1]; rows_out [B, R] int32; mask_out [B, Fv] uint32; argmax_out [B, Fv] uint8 (slot of the MAX value; 0 for the
+ *   other combiners) - the last three needed with F > 0 (mask / argmax with Fv > 0)
+ *
+ * satrans_linear_bwd:  no floating-point atomics; the same call twice gives the same bits.
+ *   contribution of slot position p = b R + r:  COPY dlogit[b]; SUM dlogit[b] at valid slots, 0 at padding; MEAN dlogit[b] /
+ *     (count + 1e-8f) at valid slots; MAX dlogit[b] at the saved argmax slot, 0 elsewhere (materialised once, [B R] floats)
+ *   g_arena[row] = the sum of its positions' contributions over (sorted_rows, src) = satrans_embed_sort(rows, n = B R,
+ *     arena_rows, ...): the sorted list is cut into chunks of SATRANS_LINEAR_SEG_CHUNK positions at multiples of that number;
+ *     inside a chunk a row's positions are added in position order; a row whose run crosses chunk bounds gets its per-chunk sums
+ *     added in chunk order (one lane per such row).  The order depends on the sorted list alone, never on the grid.  The caller
+ *     zero-fills g_arena: rows nobody gathered are not written.
+ *   dweight[k] = sum_b dense[b, dense_cols[k]] * dlogit[b]: per SATRANS_LINEAR_DW_ROW_CHUNK rows a partial (fmaf, row order),
+ *     the partials added in chunk order in fp64 (the heads' ordered reduce).  X gets no gradient.
+ *   workspace: satrans_linear_workspace_bytes(d) bytes (negative: the error code of a bad descriptor).
+ * All argument checks are made before a device is touched. */
+#define SATRANS_LINEAR_SAMPLES 16
+#define SATRANS_LINEAR_MAX_BLOCKS 512
+#define SATRANS_LINEAR_SEG_CHUNK 32
+#define SATRANS_LINEAR_DW_ROW_CHUNK 64
+typedef struct satrans_linear_desc {
+    int32_t B, F, R, Fv;
+    int32_t id_dtype, n_dense;
+    int64_t x_stride, arena_rows, dense_stride;
+    const float* arena;
+    const satrans_pool_field* fields;
+    const void* X;
+    const float* dense;
+    const int32_t* dense_cols;
+    const float* weight;
+} satrans_linear_desc;
+int64_t satrans_linear_workspace_bytes(const satrans_linear_desc* d);
+int satrans_linear_fwd(const satrans_linear_desc* d, float* logit, int32_t* rows_out, uint32_t* mask_out, uint8_t* argmax_out,
+                       int32_t* status, void* stream);
+int satrans_linear_bwd(const satrans_linear_desc* d, const float* dlogit, const int32_t* rows, const uint32_t* mask,
+                       const uint8_t* argmax, const int32_t* sorted_rows, const int32_t* src, float* g_arena, float* dweight,
+                       void* workspace, void* stream);
+
 /* Measurement aid (bench.py): the READ side of the gather alone - arena rows by row number (the `rows_out` of
  * satrans_gather_fwd), eight rows in flight per thread, nothing written but a checksum per thread into `sink`
  * (satrans_gather_read_probe_floats() floats).  This is the access pattern of the first layer with the gather fused in. */

@@ -5,7 +5,7 @@ from .callbacks import History  # noqa: F401
 from .basemodel import BaseModel  # noqa: F401
 from .satrans import SATrans  # noqa: F401
 from .layers import (CIN, FM, AdaSparseHead, AFMHead, AFMLayer, AutoIntHead, BiInteractionPooling, BilinearInteraction,  # noqa: F401
-                     CrossNet, DCNHead, DeepFMHead, ESMMHead, FiBiNETHead, InnerProductLayer, InteractingLayer, MDR_BatchNorm,
+                     CrossNet, DCNHead, DeepFMHead, ESMMHead, FeatureEmbedding, FiBiNETHead, InnerProductLayer, InteractingLayer, LinearModel, MDR_BatchNorm,
                      MetaTransformation, MMoEHead, NFMHead, OutterProductLayer, PartitionedNorm, PLEHead, PNNHead, PrunedDNN, SelfAttention_Layer, SENETLayer,
                      SharedBottomHead, StarHead, StarTowers, WDLHead, XDeepFMHead)
 
@@ -14,4 +14,4 @@ __all__ = ["SATrans", "BaseModel", "SparseFeat", "DenseFeat", "VarLenSparseFeat"
            "MDR_BatchNorm", "PartitionedNorm", "StarTowers", "StarHead", "MMoEHead", "PLEHead", "PrunedDNN", "AdaSparseHead",
            "SharedBottomHead", "CIN", "XDeepFMHead", "CrossNet", "DCNHead", "SENETLayer", "BilinearInteraction", "FiBiNETHead",
            "InnerProductLayer", "OutterProductLayer", "PNNHead", "FM", "BiInteractionPooling", "AFMLayer", "DeepFMHead", "NFMHead",
-           "AFMHead", "InteractingLayer", "AutoIntHead", "ESMMHead", "WDLHead"]
+           "AFMHead", "InteractingLayer", "AutoIntHead", "ESMMHead", "WDLHead", "LinearModel", "FeatureEmbedding"]

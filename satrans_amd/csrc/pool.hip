@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "pool_fields.h"
 
 namespace satrans {
 
@@ -22,10 +23,6 @@ constexpr int kPoolItems = SATRANS_POOL_ITEMS;
 constexpr int kPoolSlotStep = 2;
 constexpr int kPoolMaxBlocks = SATRANS_POOL_MAX_BLOCKS;      // 8 blocks per CU (256 CUs)
 static_assert(kPoolBlock == 256 && kPoolItems == 4 && kPoolMaxBlocks == 256 * 8, "the launch shape the kernels were tuned at");
-
-struct PoolFields {
-    satrans_pool_field f[SATRANS_POOL_MAX_FIELDS];
-};
 
 __device__ __forceinline__ float4 f4_zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
@@ -202,36 +199,6 @@ __global__ __launch_bounds__(kPoolBlock) void pool_bwd_kernel(const float4* __re
         f += sf;
         if (f >= F) { f -= F; ++b; }
     }
-}
-
-// Host-side check of the field table (it travels by value as a kernel argument: every row index it can produce is checked here)
-static int check_fields(const satrans_pool_field* fields, int F, int R, int Fv, int64_t x_stride, int64_t arena_rows,
-                        const char* who) {
-    SATRANS_REQUIRE(fields && F > 0 && F <= SATRANS_POOL_MAX_FIELDS, SATRANS_E_BADARG, "%s: F = %d (1..%d fields)", who, F,
-                    SATRANS_POOL_MAX_FIELDS);
-    int slot = 0, nv = 0;
-    for (int f = 0; f < F; ++f) {
-        const satrans_pool_field& d = fields[f];
-        const bool var = d.combiner != SATRANS_POOL_COPY;
-        SATRANS_REQUIRE(d.combiner >= SATRANS_POOL_COPY && d.combiner <= SATRANS_POOL_MAX, SATRANS_E_BADARG,
-                        "%s: field %d: combiner %d", who, f, d.combiner);
-        SATRANS_REQUIRE(var ? (d.maxlen >= 1 && d.maxlen <= SATRANS_POOL_MAX_LEN) : d.maxlen == 1, SATRANS_E_UNSUPPORTED,
-                        "%s: field %d: maxlen %d (1..%d)", who, f, d.maxlen, SATRANS_POOL_MAX_LEN);
-        SATRANS_REQUIRE(d.slot == slot, SATRANS_E_BADARG, "%s: field %d: first slot %d, expected %d", who, f, d.slot, slot);
-        SATRANS_REQUIRE(var ? d.varlen == nv : d.varlen == -1, SATRANS_E_BADARG, "%s: field %d: varlen index %d", who, f, d.varlen);
-        SATRANS_REQUIRE(d.col >= 0 && (int64_t)d.col + d.maxlen <= x_stride && d.len_col < x_stride &&
-                            (var || d.len_col == -1) && d.len_col >= -1, SATRANS_E_BADARG,
-                        "%s: field %d: X columns [%d, %d) / length column %d outside a row of %lld", who, f, d.col,
-                        d.col + d.maxlen, d.len_col, (long long)x_stride);
-        SATRANS_REQUIRE(d.lo >= 0 && d.lo < d.hi && d.hi <= arena_rows, SATRANS_E_BADARG,
-                        "%s: field %d: table rows [%lld, %lld) outside the arena of %lld", who, f, (long long)d.lo,
-                        (long long)d.hi, (long long)arena_rows);
-        slot += d.maxlen;
-        nv += var ? 1 : 0;
-    }
-    SATRANS_REQUIRE(slot == R && nv == Fv, SATRANS_E_BADARG, "%s: R = %d, Fv = %d; the fields give %d slots, %d varlen", who, R,
-                    Fv, slot, nv);
-    return SATRANS_OK;
 }
 
 static int64_t pool_blocks(int64_t n_items, int lpr, int per_thread) {

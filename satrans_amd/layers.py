@@ -61,21 +61,30 @@
     DNN half of WDL.forward (models/wdl.py:75-77): the same kernels at two towers and at one, with dropout inside the DNNs as a
     compile-time option of the dense layer launcher of csrc/head_layers.h, each head one autograd.Function (csrc/esmm.hip).
 
+  * `LinearModel` - deepctr's `Linear`, the order-1 term `linear_model(X)` of the reference's baselines (models/meta_basemodel.py:
+    34-92): 1-wide tables under the pooled gather's field table plus dense @ weight, one launch forward in a fixed summation
+    order, an ordered segment sum without float atomics backward (csrc/linear.hip); and `FeatureEmbedding`, the reference's
+    `input_from_feature_columns` (meta_basemodel.py:519-545) as one autograd.Function over the existing gather / pool / sort
+    ABI (csrc/gather.hip, csrc/pool.hip, csrc/embed_adam.hip).  Together they turn `X` into the `linear_logit`, `emb` and `dense`
+    that every head above starts from, with dense table gradients for any torch optimizer.
+
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
 csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip, csrc/fibinet.hip, csrc/pnn.hip, csrc/fm.hip,
-csrc/autoint.hip, csrc/esmm.hip) wrapped
+csrc/autoint.hip, csrc/esmm.hip, csrc/linear.hip) wrapped
 in a
 `torch.autograd.Function`, so they can sit inside any torch model.  There is no CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections import OrderedDict
 
 import torch
 import torch.nn as nn
 from torch.nn.modules.batchnorm import _NormBase
 
 from . import native as N
+from .basemodel import _LinearTables, make_embedding_tables
 
 NO_SCALING, NO_NORM = 128, 256
 
@@ -3039,3 +3048,374 @@ class WDLHead(_DropoutDNNHead):
                    [self.dnn_linear.weight, self.out.bias])
         logit, _ = self._run("WDLHead", 1, dnn_input, tensors)
         return logit
+
+
+# ---- the front end: X -> linear_logit, emb, dense ------------------------------------------------------------------------------
+_COMBINERS = {"sum": N.POOL_SUM, "mean": N.POOL_MEAN, "max": N.POOL_MAX}
+EMBEDDING_DIMS = (16, 32, 64, 128)      # the widths the gather, pool and optimizer kernels are built for
+
+
+class _FieldLayout:
+    """The host half of a lookup over one arena: the columns split as the reference splits them, the field table of the pooled
+    gather's ABI (`satrans_pool_field`: sparse fields, then varlen fields), the X columns of the dense values.  Every limit of
+    the kernels is checked here, at construction, as a ValueError."""
+
+    def __init__(self, what, feature_columns, feature_index):
+        from .inputs import split_columns
+        self.sparse, self.dense, self.varlen = split_columns(feature_columns)
+        self.F = len(self.sparse) + len(self.varlen)
+        self.Fv = len(self.varlen)
+        self.R = len(self.sparse) + sum(c.maxlen for c in self.varlen)
+        if self.F > N.POOL_MAX_FIELDS:
+            raise ValueError(f"{what}: {self.F} sparse and varlen fields; the kernels take up to POOL_MAX_FIELDS = {N.POOL_MAX_FIELDS}")
+        for c in self.varlen:
+            if not 1 <= c.maxlen <= N.POOL_MAX_LEN:
+                raise ValueError(f"{what}: {c.name}: maxlen {c.maxlen}; the kernels take 1..POOL_MAX_LEN = {N.POOL_MAX_LEN}")
+            if c.combiner not in _COMBINERS:
+                raise ValueError(f"{what}: {c.name}: combiner {c.combiner!r} is not one of {sorted(_COMBINERS)}")
+        for c in self.sparse + self.varlen + self.dense:
+            if c.name not in feature_index:
+                raise ValueError(f"{what}: {c.name} has no columns in feature_index")
+        for c in self.varlen:
+            if c.length_name is not None and c.length_name not in feature_index:
+                raise ValueError(f"{what}: {c.length_name} (the length of {c.name}) has no column in feature_index")
+        self.names = list(dict.fromkeys(c.embedding_name for c in self.sparse + self.varlen))      # one table per embedding_name
+        self.dense_cols = [j for c in self.dense for j in range(*feature_index[c.name])]
+        self.n_dense = len(self.dense_cols)
+        spans = [feature_index[c.name] for c in self.sparse + self.varlen + self.dense]
+        spans += [feature_index[c.length_name] for c in self.varlen if c.length_name is not None]
+        self.x_cols = max((hi for _, hi in spans), default=0)      # X needs this many columns
+        self.feature_index = feature_index
+        self.fields, self.table_rows = None, {}
+
+    def bind(self, table_rows):
+        """table_rows: embedding_name -> (first arena row, rows).  Builds the host array of satrans_pool_field."""
+        fi = self.feature_index
+        fields, slot = (N.PoolField * max(1, self.F))(), 0
+        for f, c in enumerate(self.sparse + self.varlen):
+            lo, rows = table_rows[c.embedding_name]
+            fd, var = fields[f], f >= len(self.sparse)
+            fd.col, fd.maxlen = fi[c.name][0], (c.maxlen if var else 1)
+            fd.combiner = _COMBINERS[c.combiner] if var else N.POOL_COPY
+            fd.len_col = fi[c.length_name][0] if var and c.length_name is not None else -1
+            fd.slot, fd.varlen = slot, (f - len(self.sparse) if var else -1)
+            fd.lo, fd.hi = lo, lo + rows
+            slot += fd.maxlen
+        self.fields, self.table_rows = fields, dict(table_rows)
+
+
+def _input_parts(what, X, lay):
+    """X: the reference's fp32 matrix, an integer id matrix (no dense columns then), or inputs.PackedInput(ids, dense).
+    -> (ids [B, C] contiguous, dense matrix or None, packed: the dense values are columns 0..n_dense-1 of `dense`)."""
+    from .inputs import PackedInput
+    packed = isinstance(X, PackedInput)
+    ids, dense = (X.ids, X.dense) if packed else (X, X)
+    if not torch.is_tensor(ids) or ids.dim() != 2 or ids.shape[0] < 1 or ids.shape[1] < lay.x_cols:
+        raise ValueError(f"{what}: expected X [B, >= {lay.x_cols}], got {tuple(ids.shape) if torch.is_tensor(ids) else type(ids)}")
+    N.require_gpu(ids, what)
+    N.id_dtype_of(ids)
+    if not packed and ids.dtype != torch.float32:
+        dense = None
+    if lay.n_dense:
+        if dense is None or dense.dtype != torch.float32:
+            raise TypeError(f"{what}: the dense columns need a float32 X or a PackedInput with a float32 dense block")
+        if packed and (dense.dim() != 2 or tuple(dense.shape) != (ids.shape[0], lay.n_dense) or dense.device != ids.device):
+            raise ValueError(f"{what}: PackedInput.dense must be [{ids.shape[0]}, {lay.n_dense}] beside the ids, got {tuple(dense.shape)}")
+        dense = dense.contiguous()
+    else:
+        dense = None
+    return ids.contiguous(), dense, packed
+
+
+class _TableArena:
+    """What LinearModel and FeatureEmbedding share: the tables of `embedding_dict` as views of ONE arena (rebuilt after every
+    `.to()`, as BaseModel._rebind_storage), the field table over it, the device-side column lists and the status word."""
+
+    def _rebind_storage(self):
+        lay = self._layout
+        tables = [self.embedding_dict[n].weight for n in lay.names]
+        rows, off = OrderedDict(), 0
+        for n, t in zip(lay.names, tables):
+            rows[n] = (off, t.shape[0])
+            off += t.shape[0]
+        self.arena = None
+        dev = tables[0].device if tables else (self.weight.device if getattr(self, "weight", None) is not None else torch.device("cpu"))
+        if tables:
+            self.arena = torch.cat([t.data.reshape(t.shape[0], -1) for t in tables], dim=0).contiguous()
+            for n, t in zip(lay.names, tables):
+                lo, cnt = rows[n]
+                t.data = self.arena[lo:lo + cnt]
+        lay.bind(rows)
+        i32 = dict(dtype=torch.int32, device=dev)
+        self._dense_cols_x = torch.tensor(lay.dense_cols, **i32)
+        self._dense_cols_packed = torch.arange(lay.n_dense, **i32)
+        self._status = torch.zeros(1, **i32)
+        sp = [f for f in lay.fields[:lay.F]]
+        self._gather_cols = torch.tensor([f.col for f in sp], **i32)
+        self._row_span = torch.tensor([[f.lo, f.hi] for f in sp], dtype=torch.int64, device=dev).reshape(-1, 2)
+
+    def _apply(self, fn, *args, **kwargs):
+        out = super()._apply(fn, *args, **kwargs)
+        if getattr(self, "_layout", None) is not None:
+            self._rebind_storage()
+        return out
+
+    def _tables(self):
+        """The tables in arena order, still views of the arena (a `.data` assignment from outside is folded back in)."""
+        lay = self._layout
+        tables = [self.embedding_dict[n].weight for n in lay.names]
+        width = self.arena.shape[1] * 4
+        if any(t.data_ptr() != self.arena.data_ptr() + lay.table_rows[n][0] * width for n, t in zip(lay.names, tables)):
+            self._rebind_storage()
+        return tables
+
+    def _raise_on_status(self, what):
+        """One device-to-host read per forward; the word is cleared before raising, so the next call starts clean."""
+        flags = int(self._status.item())
+        if flags:
+            self._status.zero_()
+            if flags & 1:
+                raise IndexError(f"index out of range in self: {what}: an id lies outside its table")
+            raise N.NativeError(f"{what}: a dense column lies outside the dense matrix")
+
+    def _table_grads(self, g_arena):
+        return [g_arena[lo:lo + cnt] for lo, cnt in (self._layout.table_rows[n] for n in self._layout.names)]
+
+
+def _sorted_positions(lib, rows, n, arena_rows, dev):
+    """satrans_embed_sort over the n slot rows of a batch -> (sorted_rows, src), equal rows in position order."""
+    i32 = dict(dtype=torch.int32, device=dev)
+    sorted_rows, src = torch.empty(n, **i32), torch.empty(n, **i32)
+    nbytes = int(lib.satrans_embed_sort_workspace_bytes(n, arena_rows))
+    ws = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+    N.check(lib.satrans_embed_sort(rows.data_ptr(), n, arena_rows, sorted_rows.data_ptr(), src.data_ptr(), None, ws.data_ptr(),
+                                   ws.numel(), None, N.stream_handle(dev)), "satrans_embed_sort")
+    return sorted_rows, src
+
+
+def _linear_desc(mod, ids, dense, packed, weight):
+    lay = mod._layout
+    d = N.LinearDesc()
+    d.B, d.F, d.R, d.Fv = ids.shape[0], lay.F, lay.R, lay.Fv
+    d.id_dtype, d.n_dense = N.id_dtype_of(ids), lay.n_dense
+    d.x_stride, d.arena_rows = ids.shape[1], (mod.arena.shape[0] if mod.arena is not None else 0)
+    d.arena = mod.arena.data_ptr() if mod.arena is not None else None
+    d.fields = C.cast(lay.fields, C.POINTER(N.PoolField)) if lay.F else None
+    d.X = ids.data_ptr()
+    if lay.n_dense:
+        d.dense, d.dense_stride = dense.data_ptr(), dense.shape[1]
+        d.dense_cols = (mod._dense_cols_packed if packed else mod._dense_cols_x).data_ptr()
+        d.weight = weight.data_ptr()
+    return d
+
+
+class _LinearFn(torch.autograd.Function):
+    """linear_logit [B, 1] of LinearModel (csrc/linear.hip).  `params`: the tables in arena order (views of mod.arena, which the
+    kernels read), then `weight` when there are dense columns; their gradients: slices of one zero-filled [arena_rows, 1] buffer,
+    and dweight."""
+
+    @staticmethod
+    def forward(ctx, mod, ids, dense, packed, *params):
+        lib = N.lib()
+        dev, lay = ids.device, mod._layout
+        B = ids.shape[0]
+        weight = params[-1].contiguous() if lay.n_dense else None
+        d = _linear_desc(mod, ids, dense, packed, weight)
+        logit = torch.empty(B, 1, dtype=torch.float32, device=dev)
+        rows = torch.empty(B, lay.R, dtype=torch.int32, device=dev)
+        mask = torch.empty(B, lay.Fv, dtype=torch.int32, device=dev)
+        argmax = torch.empty(B, lay.Fv, dtype=torch.uint8, device=dev)
+        N.check(lib.satrans_linear_fwd(C.byref(d), logit.data_ptr(), rows.data_ptr(), mask.data_ptr(), argmax.data_ptr(),
+                                       mod._status.data_ptr(), N.stream_handle(dev)), "satrans_linear_fwd")
+        mod._raise_on_status("LinearModel")
+        ctx.mod, ctx.packed, ctx.ids, ctx.dense = mod, packed, ids, dense
+        ctx.save_for_backward(rows, mask, argmax, *([weight] if lay.n_dense else []))
+        return logit
+
+    @staticmethod
+    def backward(ctx, dlogit):
+        lib = N.lib()
+        mod, lay, ids = ctx.mod, ctx.mod._layout, ctx.ids
+        rows, mask, argmax, *w = ctx.saved_tensors
+        dev = ids.device
+        d = _linear_desc(mod, ids, ctx.dense, ctx.packed, w[0] if w else None)
+        dlogit = dlogit.contiguous().float()
+        f32 = dict(dtype=torch.float32, device=dev)
+        g_arena = sorted_rows = src = dweight = None
+        if lay.F:
+            sorted_rows, src = _sorted_positions(lib, rows, rows.numel(), d.arena_rows, dev)
+            g_arena = torch.zeros(d.arena_rows, 1, **f32)
+        if lay.n_dense:
+            dweight = torch.empty(lay.n_dense, 1, **f32)
+        work = torch.empty(max(256, _native_size(lib.satrans_linear_workspace_bytes, d)), dtype=torch.uint8, device=dev)
+        N.check(lib.satrans_linear_bwd(C.byref(d), dlogit.data_ptr(), rows.data_ptr(), mask.data_ptr(), argmax.data_ptr(),
+                                       N.ptr(sorted_rows), N.ptr(src), N.ptr(g_arena), N.ptr(dweight), work.data_ptr(),
+                                       N.stream_handle(dev)), "satrans_linear_bwd")
+        grads = (mod._table_grads(g_arena) if lay.F else []) + ([dweight] if lay.n_dense else [])
+        return (None, None, None, None, *grads)
+
+
+class LinearModel(_TableArena, _LinearTables):
+    """deepctr's `Linear`, the order-1 term `linear_model(X)` of the reference's WDL, DCN, DeepFM, xDeepFM, NFM, AFM and FiBiNET
+    (models/meta_basemodel.py:34-92):
+
+        forward(X) -> linear_logit [B, 1] = sum over the sparse fields, then the pooled varlen fields, of their 1-wide
+                      embeddings + cat(dense values) @ weight
+
+    X is the reference's fp32 matrix in `feature_index` column order, or inputs.PackedInput(ids, dense) (integer ids; `dense`
+    holds this module's dense values in concatenation order), or a bare integer matrix when there is no DenseFeat.  ONE
+    autograd.Function over satrans_linear_fwd / satrans_linear_bwd (csrc/linear.hip): one launch forward - the summation order is
+    fixed (fields in the reference's list order, then the dense products ascending, fp32; satrans_hip.h) and a sample's logit
+    does not depend on its batch - and, backward, satrans_embed_sort plus an ordered segment sum without float atomics: the same
+    call twice gives the same bits.  The pooling rules are the pooled gather's (sum / mean / max, mask by the length column or
+    by id != 0).  An id outside its table raises IndexError from the forward (one status read per call).
+
+    Parameters, their creation order and the generator draws are the reference's (`_LinearTables`: the tables drawn twice,
+    then `weight`): state_dict keys `embedding_dict.<embedding_name>.weight` [V, 1] and `weight` [n_dense, 1] (absent without a
+    DenseFeat); fields sharing an embedding_name share one parameter.  The tables are views of one 1-wide arena (`self.arena`),
+    rebound after `.to()`.  This is the reference's sparse=False semantics: every table receives a DENSE gradient, a slice of one
+    zero-filled [rows, 1] buffer, so any torch optimizer trains it.  Without sparse and varlen columns the result is the dense
+    term alone; without dense columns there is no `weight`; with neither, zeros [B, 1] (the reference's).
+    Not built: `sparse_feat_refine_weight` (IFM / DIFM; NotImplementedError - the reference never passes it), sparse-COO
+    gradients, a fused optimizer step for these tables, bf16, one sort shared with FeatureEmbedding."""
+
+    def __init__(self, feature_columns, feature_index, init_std=0.0001, device='cpu'):
+        lay = _FieldLayout("LinearModel", feature_columns, feature_index)      # (refuses before a generator draw is made)
+        super().__init__(feature_columns, init_std)
+        self.feature_index, self.device = feature_index, device
+        self.sparse_feature_columns, self.dense_feature_columns = lay.sparse, lay.dense
+        self.varlen_sparse_feature_columns = lay.varlen
+        self._layout = lay
+        self._rebind_storage()
+        self.to(device)
+
+    def forward(self, X, sparse_feat_refine_weight=None):
+        if sparse_feat_refine_weight is not None:
+            raise NotImplementedError("LinearModel: sparse_feat_refine_weight (IFM / DIFM) is not built")
+        lay = self._layout
+        if lay.F == 0 and lay.n_dense == 0:
+            ids = X.ids if not torch.is_tensor(X) else X
+            return torch.zeros(ids.shape[0], 1, dtype=torch.float32, device=ids.device)
+        ids, dense, packed = _input_parts("LinearModel", X, lay)
+        params = (self._tables() if lay.F else []) + ([self.weight] if lay.n_dense else [])
+        if any(p.dtype != torch.float32 for p in params):
+            raise TypeError("LinearModel: tables, weight and gradients are float32")
+        if any(p.device != ids.device for p in params):
+            raise N.NativeError(f"LinearModel: X is on {ids.device}, the parameters on {params[0].device}")
+        return _LinearFn.apply(self, ids, dense, packed, *params)
+
+
+class _FeatureEmbeddingFn(torch.autograd.Function):
+    """emb [B, F, D] of FeatureEmbedding over the existing ABI: satrans_gather_fwd (no varlen column) or satrans_pool_gather_fwd;
+    backward satrans_pool_bwd (varlen only), satrans_embed_sort, then the dense gradient into a zero-filled [rows, D] by
+    satrans_embed_segment_sums or satrans_embed_grad_dense(l2 = 0) (FeatureEmbedding.dense_gradient)."""
+
+    @staticmethod
+    def forward(ctx, mod, ids, *tables):
+        lib = N.lib()
+        dev, lay, arena = ids.device, mod._layout, mod.arena
+        B, D = ids.shape[0], arena.shape[1]
+        emb = torch.empty(B, lay.F, D, dtype=torch.float32, device=dev)
+        rows = torch.empty(B, lay.R, dtype=torch.int32, device=dev)
+        mask = argmax = None
+        st = N.stream_handle(dev)
+        if lay.Fv == 0:
+            N.check(lib.satrans_gather_fwd(arena.data_ptr(), mod._row_span.data_ptr(), mod._gather_cols.data_ptr(), ids.data_ptr(),
+                                           N.id_dtype_of(ids), ids.shape[1], B, lay.F, D, emb.data_ptr(), rows.data_ptr(),
+                                           mod._status.data_ptr(), st), "satrans_gather_fwd")
+        else:
+            mask = torch.empty(B, lay.Fv, dtype=torch.int32, device=dev)
+            argmax = torch.empty(int(lib.satrans_pool_argmax_bytes(B, lay.Fv, D)), dtype=torch.uint8, device=dev)
+            N.check(lib.satrans_pool_gather_fwd(arena.data_ptr(), arena.shape[0], None, None, lay.fields, lay.F, lay.R, lay.Fv,
+                                                ids.data_ptr(), N.id_dtype_of(ids), ids.shape[1], B, D, emb.data_ptr(),
+                                                rows.data_ptr(), mask.data_ptr(), argmax.data_ptr(), mod._status.data_ptr(), st),
+                    "satrans_pool_gather_fwd")
+        mod._raise_on_status("FeatureEmbedding")
+        ctx.mod = mod
+        ctx.save_for_backward(rows, *([mask, argmax] if lay.Fv else []))
+        return emb
+
+    @staticmethod
+    def backward(ctx, demb):
+        lib = N.lib()
+        mod, lay, arena = ctx.mod, ctx.mod._layout, ctx.mod.arena
+        rows, *pooled = ctx.saved_tensors
+        dev, st = rows.device, N.stream_handle(rows.device)
+        B, D, total = rows.shape[0], arena.shape[1], arena.shape[0]
+        gemb = demb.contiguous().float()
+        if lay.Fv:
+            dx, gemb = gemb, torch.empty(B * lay.R, D, dtype=torch.float32, device=dev)
+            N.check(lib.satrans_pool_bwd(dx.data_ptr(), lay.fields, lay.F, lay.R, lay.Fv, B, D, pooled[0].data_ptr(),
+                                         pooled[1].data_ptr(), gemb.data_ptr(), st), "satrans_pool_bwd")
+        n = B * lay.R
+        sorted_rows, src = _sorted_positions(lib, rows, n, total, dev)
+        g_arena = torch.zeros(total, D, dtype=torch.float32, device=dev)
+        if mod.dense_gradient == "segment_sums":      # the engine's chunked ordered sums, stored instead of applied
+            part = torch.empty(int(lib.satrans_embed_partial_ws_floats(n, D)), dtype=torch.float32, device=dev)
+            unused = torch.empty(int(lib.satrans_embed_reg_partials(total, n, D)), dtype=torch.float64, device=dev)
+            N.check(lib.satrans_embed_segment_sums(sorted_rows.data_ptr(), src.data_ptr(), n, gemb.data_ptr(), D, part.data_ptr(),
+                                                   unused.data_ptr(), g_arena.data_ptr(), st), "satrans_embed_segment_sums")
+        else:                                         # one lane group per run, walked in position order
+            N.check(lib.satrans_embed_grad_dense(arena.data_ptr(), sorted_rows.data_ptr(), src.data_ptr(), n, gemb.data_ptr(), total,
+                                                 D, 0.0, g_arena.data_ptr(), st), "satrans_embed_grad_dense")
+        return (None, None, *mod._table_grads(g_arena))
+
+
+class FeatureEmbedding(_TableArena, nn.Module):
+    """The reference's `input_from_feature_columns` (models/meta_basemodel.py:519-545) as one module - what every sibling head
+    starts from:
+
+        forward(X) -> (emb [B, F, D] fp32, dense [B, n_dense] fp32 or None)      F = the sparse fields, then the varlen fields
+
+    `embedding_dict` is `make_embedding_tables`' (the reference's keys, generator draws and sharing by embedding_name; state_dict
+    keys `embedding_dict.<embedding_name>.weight`); the tables are views of one arena [rows, D] (`self.arena`), rebound after
+    `.to()`.  No kernel of its own: ONE autograd.Function over the existing ABI - satrans_gather_fwd without varlen columns (every
+    element a copy: bit-exact), else satrans_pool_gather_fwd; backward satrans_pool_bwd (varlen only), satrans_embed_sort, and
+    the per-row sums of the sorted gradient rows stored into the dense buffer - no float atomics, the same bits every run.
+    `dense_gradient` picks the kernel of that last step: "segment_sums" (default; satrans_embed_segment_sums, the engine's
+    chunked ordered sums, which split a row that thousands of samples gather) or "grad_dense" (satrans_embed_grad_dense, one
+    lane group walking each row's run in position order: 2.6 ms against 0.41 ms, and the torch form's 2.1 ms, at AliCCP shape, where four
+    fields have 4 to 15 ids for 8192 samples; profiles/input_time.txt).  `dense` is the X columns of the DenseFeats
+    (PackedInput.dense as it is) and carries no gradient; X as in LinearModel.  An id outside its table raises IndexError.
+
+    This is the reference's sparse=False semantics: every table's gradient is DENSE, a slice of one zero-filled [rows, D] buffer
+    in which every row exists.  At AliCCP size (about 6.6 M rows) that buffer is 0.84 GB at D = 32: it is zero-filled and
+    written every backward and read again, with two moment buffers of the same size, by a dense optimizer step - against a few
+    MB of gathered rows.  The lazy, touched-rows-only Adam step of the SATrans engine is not available here; a model that needs it
+    is built behind BaseModel.
+    embedding_dim must be one of {16, 32, 64, 128} and the same for every field, at most POOL_MAX_FIELDS fields and
+    POOL_MAX_LEN slots per list: ValueError at construction.
+    Not built: sparse-COO gradients, a fused optimizer step for these tables, bf16, one sort shared with LinearModel, baseline
+    model classes behind BaseModel."""
+
+    def __init__(self, feature_columns, feature_index, init_std=0.0001, device='cpu'):
+        lay = _FieldLayout("FeatureEmbedding", feature_columns, feature_index)
+        if lay.F == 0:
+            raise ValueError("FeatureEmbedding: no SparseFeat or VarLenSparseFeat column (there is no emb to return)")
+        dims = sorted({c.embedding_dim for c in lay.sparse + lay.varlen})
+        if len(dims) != 1 or dims[0] not in EMBEDDING_DIMS:
+            raise ValueError(f"FeatureEmbedding: embedding_dim {dims} must be one value of {{16, 32, 64, 128}} for every field")
+        super().__init__()
+        self.feature_index, self.device = feature_index, device
+        self.embedding_size = dims[0]
+        self.dense_gradient = "segment_sums"
+        self.embedding_dict = make_embedding_tables(feature_columns, init_std)
+        self._layout = lay
+        self._rebind_storage()
+        self.to(device)
+
+    def forward(self, X):
+        from .inputs import PackedInput
+        lay = self._layout
+        ids, dense, packed = _input_parts("FeatureEmbedding", X, lay)
+        tables = self._tables()
+        if any(t.dtype != torch.float32 for t in tables):
+            raise TypeError("FeatureEmbedding: tables and gradients are float32")
+        if tables[0].device != ids.device:
+            raise N.NativeError(f"FeatureEmbedding: X is on {ids.device}, the tables on {tables[0].device}")
+        emb = _FeatureEmbeddingFn.apply(self, ids, *tables)
+        if dense is not None and not packed:
+            lo = lay.dense_cols[0]
+            contiguous = lay.dense_cols == list(range(lo, lo + lay.n_dense))
+            dense = dense[:, lo:lo + lay.n_dense] if contiguous else dense.index_select(1, self._dense_cols_x.long())
+        return emb, (dense.detach() if dense is not None else None)

@@ -405,6 +405,18 @@ GATHER_BLOCK, GATHER_ROWS_PER_THREAD, GATHER_MAX_BLOCKS = 256, 4, 2048      # SA
 POOL_BLOCK, POOL_ITEMS, POOL_MAX_BLOCKS = 256, 4, 2048                      # SATRANS_POOL_BLOCK / _ITEMS / _MAX_BLOCKS
 
 
+LINEAR_SAMPLES, LINEAR_MAX_BLOCKS = 16, 512      # SATRANS_LINEAR_SAMPLES / _MAX_BLOCKS: the grid of satrans_linear_fwd
+LINEAR_SEG_CHUNK = 32                             # SATRANS_LINEAR_SEG_CHUNK: sorted positions per partial of the row gradients
+LINEAR_DW_ROW_CHUNK = 64                          # SATRANS_LINEAR_DW_ROW_CHUNK: rows per partial of dweight
+
+
+class LinearDesc(C.Structure):
+    """Mirror of `satrans_linear_desc` (the order-1 term: 1-wide tables under the pooled gather's field table, and dense @ weight)."""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("R", C.c_int32), ("Fv", C.c_int32), ("id_dtype", C.c_int32),
+                ("n_dense", C.c_int32), ("x_stride", C.c_int64), ("arena_rows", C.c_int64), ("dense_stride", C.c_int64),
+                ("arena", _vp), ("fields", C.POINTER(PoolField)), ("X", _vp), ("dense", _vp), ("dense_cols", _vp), ("weight", _vp)]
+
+
 class AdamHParams(C.Structure):
     """Mirror of `satrans_adam_hparams`."""
     _fields_ = [("lr_over_bc1", C.c_float), ("bc2_sqrt", C.c_float), ("beta1", C.c_float),
@@ -453,6 +465,9 @@ SIGNATURES = {
                                           C.c_int64, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "satrans_pool_bwd": (C.c_int, [_vp, C.POINTER(PoolField), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "satrans_gather_read_probe": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, _vp, _vp]),
+    "satrans_linear_workspace_bytes": (C.c_int64, [C.POINTER(LinearDesc)]),
+    "satrans_linear_fwd": (C.c_int, [C.POINTER(LinearDesc), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "satrans_linear_bwd": (C.c_int, [C.POINTER(LinearDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "satrans_set_layer_impl": (C.c_int, [C.c_int]),
     "satrans_layer_fused_supported": (C.c_int, [C.POINTER(LayerDesc)]),
     "satrans_layer_fwd": (C.c_int, [C.POINTER(LayerDesc), _vp, _vp, _vp]),
