@@ -1435,6 +1435,26 @@ int satrans_embed_lazy_flush(float* arena, float* m, float* v, int32_t* last, in
                              void* stream);
 int satrans_embed_lazy_mark(const int32_t* sorted_rows, int64_t n, int32_t* last, int t, void* stream);
 
+/* The lazy form for 1-wide tables (LinearModel's arena [arena_rows, 1]; additive under ABI 7): the bits of
+ * satrans_adam_flat(h.l2) over a dense gradient buffer that is zero for every row nobody gathered, at touched-rows cost.
+ *   last, table, h   as above (replay and flush take lr_over_bc1 / bc2_sqrt of step s from table[s])
+ * satrans_embed1_lazy_replay: every slot row of a batch to step `target`, BEFORE satrans_linear_fwd reads it.  The rows are
+ *   `rows` [n] when given (any order, duplicates allowed, rows outside the arena skipped), otherwise those of X [B, x_stride]
+ *   through `fields` (F fields, R slots: satrans_linear_fwd's index arithmetic - every slot of a list, an id outside its table
+ *   counts as the table's first row).  Duplicates are settled by an integer atomic maximum on last[row]: no sort, and the
+ *   result does not depend on which lane wins.
+ * satrans_embed1_adam_rows: step t of the distinct rows of a sorted list with g[row] + 2 l2 p, then last[row] = t and
+ *   g[row] = 0 - `g` [arena_rows] is the buffer satrans_linear_bwd stored its sums in, and is all-zero again afterwards.
+ * satrans_embed1_lazy_flush: every row to step `target`. */
+int satrans_embed1_lazy_replay(float* arena, float* m, float* v, int32_t* last, int64_t arena_rows, const int32_t* rows,
+                               int64_t n, const satrans_pool_field* fields, int F, int R, const void* X, int id_dtype,
+                               int64_t x_stride, int B, int target, const double* table, const satrans_adam_hparams* h,
+                               void* stream);
+int satrans_embed1_adam_rows(float* arena, float* m, float* v, int32_t* last, float* g, int64_t arena_rows,
+                             const int32_t* sorted_rows, int64_t n, const satrans_adam_hparams* h, int t, void* stream);
+int satrans_embed1_lazy_flush(float* arena, float* m, float* v, int32_t* last, int64_t arena_rows, int target,
+                              const double* table, const satrans_adam_hparams* h, void* stream);
+
 /* Diagnostic behind the replay's arithmetic.  Replay and flush run four elements per lane on the packed fp32 pipe with the
  * square root and the division written out as correctly rounded fma sequences (embed_adam.hip); this call counts the results
  * that differ from the IEEE operations: mode 0 = square root over the floats with bit patterns [first, first + count),

@@ -8,10 +8,11 @@ from .layers import (CIN, FM, AdaSparseHead, AFMHead, AFMLayer, AutoIntHead, BiI
                      CrossNet, DCNHead, DeepFMHead, ESMMHead, FeatureEmbedding, FiBiNETHead, InnerProductLayer, InteractingLayer, LinearModel, MDR_BatchNorm,
                      MetaTransformation, MMoEHead, NFMHead, OutterProductLayer, PartitionedNorm, PLEHead, PNNHead, PrunedDNN, SelfAttention_Layer, SENETLayer,
                      SharedBottomHead, StarHead, StarTowers, WDLHead, XDeepFMHead)
+from .optim import TableAdam  # noqa: F401
 
 __all__ = ["SATrans", "BaseModel", "SparseFeat", "DenseFeat", "VarLenSparseFeat", "get_feature_names",
            "build_input_features", "History", "SelfAttention_Layer", "MetaTransformation",
            "MDR_BatchNorm", "PartitionedNorm", "StarTowers", "StarHead", "MMoEHead", "PLEHead", "PrunedDNN", "AdaSparseHead",
            "SharedBottomHead", "CIN", "XDeepFMHead", "CrossNet", "DCNHead", "SENETLayer", "BilinearInteraction", "FiBiNETHead",
            "InnerProductLayer", "OutterProductLayer", "PNNHead", "FM", "BiInteractionPooling", "AFMLayer", "DeepFMHead", "NFMHead",
-           "AFMHead", "InteractingLayer", "AutoIntHead", "ESMMHead", "WDLHead", "LinearModel", "FeatureEmbedding"]
+           "AFMHead", "InteractingLayer", "AutoIntHead", "ESMMHead", "WDLHead", "LinearModel", "FeatureEmbedding", "TableAdam"]

@@ -1640,3 +1640,141 @@ extern "C" int satrans_optim_flat(int kind, float* p, const float* g, float* sta
     SATRANS_CHECK_LAUNCH("optim_flat_kernel");
     return SATRANS_OK;
 }
+
+
+// ---- 1-wide tables (LinearModel): the lazy form of the dense satrans_adam_flat(l2) sweep -------------------------------------------
+// A row is one float, so a lane owns a whole row and there is nothing to share inside a wave: each kernel is adam1 with the AdamK
+// that make_adamk would build for the step at hand (neg_step, rbc2, rbc2f from the per-step table, the rest from `h`), i.e. the bits
+// of adam_flat_kernel over a gradient buffer that is zero for every row nobody gathered.
+//   replay  every slot row of a batch - from X through the field table (the index arithmetic of linear_fwd_kernel) or from a row
+//           list - is brought to `target` before the forward reads it.  No sort: duplicates are settled by an integer atomicMax on
+//           last[row], whose return value tells exactly one lane the step the row stood at; the others find `target` and leave.
+//   step    one lane per run head of the backward's sorted list: g[row] + 2 l2 p, last[row] = t, and g[row] back to zero, so the
+//           gradient buffer is all-zero between steps without a sweep.
+//   flush   one lane per row, its pending steps in order.
+#include "pool_fields.h"
+
+namespace satrans {
+
+__device__ __forceinline__ void embed1_replay_row(float* __restrict__ P, float* __restrict__ M, float* __restrict__ V, int64_t row,
+                                                  int from, int to, const double2* __restrict__ table, AdamK k) {
+    float p = P[row], m = M[row], v = V[row];
+    for (int s = from + 1; s <= to; ++s) {
+        const double2 hp = table[s];
+        k.neg_step = -(float)hp.x;
+        k.rbc2 = hp.y;
+        k.rbc2f = (float)hp.y;
+        adam1(p, m, v, __fadd_rn(0.f, __fmul_rn(k.l2x2, p)), k);      // (the dense form's g[row] = +0 for a row nobody gathered)
+    }
+    P[row] = p; M[row] = m; V[row] = v;
+}
+
+__global__ __launch_bounds__(256) void embed1_replay_kernel(float* __restrict__ P, float* __restrict__ M, float* __restrict__ V,
+                                                           int32_t* __restrict__ last, int64_t arena_rows,
+                                                           const int32_t* __restrict__ rows, int64_t n, const PoolFields pf, int F,
+                                                           const void* __restrict__ X, int id_dtype, int64_t x_stride, int target,
+                                                           const double2* __restrict__ table, AdamK k) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t item = (int64_t)blockIdx.x * 256 + threadIdx.x; item < n; item += stride) {
+        int slots = 1;
+        int64_t b = 0;
+        satrans_pool_field fd = pf.f[0];
+        if (!rows) {                                  // item = (sample, field): every slot of the list, padding slots included
+            b = item / F;
+            fd = pf.f[(int)(item - b * F)];
+            slots = fd.maxlen;
+        }
+        for (int s = 0; s < slots; ++s) {
+            int64_t row;
+            if (rows) {
+                row = rows[item];
+            } else {
+                const int64_t id = load_id(X, id_dtype, x_stride, b, fd.col + s);
+                row = (id < 0 || id >= fd.hi - fd.lo) ? fd.lo : fd.lo + id;      // (out of range: the forward flags it)
+            }
+            if (row < 0 || row >= arena_rows) continue;
+            const int prev = atomicMax(&last[row], target);
+            if (prev < target) embed1_replay_row(P, M, V, row, prev, target, table, k);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void embed1_step_kernel(float* __restrict__ P, float* __restrict__ M, float* __restrict__ V,
+                                                         int32_t* __restrict__ last, float* __restrict__ G, int64_t arena_rows,
+                                                         const int32_t* __restrict__ sorted_rows, int64_t n, int t, const AdamK k) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= n) return;
+    const int64_t row = sorted_rows[j];
+    if ((j > 0 && sorted_rows[j - 1] == row) || row < 0 || row >= arena_rows) return;
+    float p = P[row], m = M[row], v = V[row];
+    adam1(p, m, v, __fadd_rn(G[row], __fmul_rn(k.l2x2, p)), k);
+    P[row] = p; M[row] = m; V[row] = v;
+    last[row] = t;
+    G[row] = 0.f;
+}
+
+__global__ __launch_bounds__(256) void embed1_flush_kernel(float* __restrict__ P, float* __restrict__ M, float* __restrict__ V,
+                                                          int32_t* __restrict__ last, int64_t arena_rows, int target,
+                                                          const double2* __restrict__ table, const AdamK k) {
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < arena_rows; row += stride) {
+        const int from = last[row];
+        if (from >= target) continue;
+        embed1_replay_row(P, M, V, row, from, target, table, k);
+        last[row] = target;
+    }
+}
+
+}  // namespace satrans
+
+extern "C" int satrans_embed1_lazy_replay(float* arena, float* m, float* v, int32_t* last, int64_t arena_rows, const int32_t* rows,
+                                          int64_t n, const satrans_pool_field* fields, int F, int R, const void* X, int id_dtype,
+                                          int64_t x_stride, int B, int target, const double* table,
+                                          const satrans_adam_hparams* h, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SATRANS_REQUIRE(arena && m && v && last && table && h && arena_rows > 0 && target >= 0, SATRANS_E_BADARG,
+                    "embed1_lazy_replay: null pointer, arena_rows = %lld or target = %d", (long long)arena_rows, target);
+    PoolFields pf = pool_fields_of(nullptr, 0);
+    int64_t items = n;
+    if (rows) {
+        SATRANS_REQUIRE(n > 0, SATRANS_E_BADARG, "embed1_lazy_replay: n = %lld rows", (long long)n);
+    } else {
+        SATRANS_REQUIRE(X && B > 0, SATRANS_E_BADARG, "embed1_lazy_replay: neither a row list nor X");
+        SATRANS_REQUIRE(id_dtype == SATRANS_ID_F32 || id_dtype == SATRANS_ID_I32 || id_dtype == SATRANS_ID_I64, SATRANS_E_BADARG,
+                        "embed1_lazy_replay: id_dtype %d", id_dtype);
+        int Fv = 0;
+        for (int f = 0; fields && f < F && f < SATRANS_POOL_MAX_FIELDS; ++f) Fv += fields[f].combiner != SATRANS_POOL_COPY;
+        if (int rc = check_fields(fields, F, R, Fv, x_stride, arena_rows, "embed1_lazy_replay")) return rc;
+        pf = pool_fields_of(fields, F);
+        items = (int64_t)B * F;
+    }
+    const int64_t blocks = std::min<int64_t>(ceil_div(items, 256), 4096);      // grid-strided beyond
+    embed1_replay_kernel<<<(unsigned)blocks, 256, 0, stream>>>(arena, m, v, last, arena_rows, rows, items, pf, F, X, id_dtype, x_stride,
+                                                              target, (const double2*)table, make_adamk(*h));
+    SATRANS_CHECK_LAUNCH("embed1_replay_kernel");
+    return SATRANS_OK;
+}
+
+extern "C" int satrans_embed1_adam_rows(float* arena, float* m, float* v, int32_t* last, float* g, int64_t arena_rows,
+                                        const int32_t* sorted_rows, int64_t n, const satrans_adam_hparams* h, int t, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SATRANS_REQUIRE(arena && m && v && last && g && sorted_rows && h, SATRANS_E_BADARG, "embed1_adam_rows: null pointer");
+    SATRANS_REQUIRE(n > 0 && n < ((int64_t)1 << 31) * 256 && arena_rows > 0, SATRANS_E_BADARG,
+                    "embed1_adam_rows: n = %lld, arena_rows = %lld", (long long)n, (long long)arena_rows);
+    embed1_step_kernel<<<(unsigned)ceil_div(n, 256), 256, 0, stream>>>(arena, m, v, last, g, arena_rows, sorted_rows, n, t,
+                                                                      make_adamk(*h));
+    SATRANS_CHECK_LAUNCH("embed1_step_kernel");
+    return SATRANS_OK;
+}
+
+extern "C" int satrans_embed1_lazy_flush(float* arena, float* m, float* v, int32_t* last, int64_t arena_rows, int target,
+                                         const double* table, const satrans_adam_hparams* h, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SATRANS_REQUIRE(arena && m && v && last && table && h && arena_rows > 0 && target >= 0, SATRANS_E_BADARG,
+                    "embed1_lazy_flush: null pointer, arena_rows = %lld or target = %d", (long long)arena_rows, target);
+    const int64_t blocks = std::min<int64_t>(ceil_div(arena_rows, 256), 4096);
+    embed1_flush_kernel<<<(unsigned)blocks, 256, 0, stream>>>(arena, m, v, last, arena_rows, target, (const double2*)table,
+                                                             make_adamk(*h));
+    SATRANS_CHECK_LAUNCH("embed1_flush_kernel");
+    return SATRANS_OK;
+}

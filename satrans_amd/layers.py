@@ -66,7 +66,8 @@
     order, an ordered segment sum without float atomics backward (csrc/linear.hip); and `FeatureEmbedding`, the reference's
     `input_from_feature_columns` (meta_basemodel.py:519-545) as one autograd.Function over the existing gather / pool / sort
     ABI (csrc/gather.hip, csrc/pool.hip, csrc/embed_adam.hip).  Together they turn `X` into the `linear_logit`, `emb` and `dense`
-    that every head above starts from, with dense table gradients for any torch optimizer.
+    that every head above starts from, with dense table gradients for any torch optimizer - or, adopted by optim.TableAdam, the
+    engine's touched-rows lazy Adam step with no dense gradient at all.
 
 All are ordinary `nn.Module`s whose forward/backward are HIP launches (csrc/layer_generic.hip, csrc/pnorm.hip, csrc/star.hip,
 csrc/mmoe.hip, csrc/ple.hip, csrc/adasparse.hip, csrc/cin.hip, csrc/cross.hip, csrc/fibinet.hip, csrc/pnn.hip, csrc/fm.hip,
@@ -3212,7 +3213,8 @@ def _linear_desc(mod, ids, dense, packed, weight):
 class _LinearFn(torch.autograd.Function):
     """linear_logit [B, 1] of LinearModel (csrc/linear.hip).  `params`: the tables in arena order (views of mod.arena, which the
     kernels read), then `weight` when there are dense columns; their gradients: slices of one zero-filled [arena_rows, 1] buffer,
-    and dweight."""
+    and dweight.  Adopted by an optim.TableAdam: the lazy 1-wide form first replays the batch's slot rows; the backward stores the
+    row sums into the optimizer's buffer, hands it (sorted_rows, dweight) and returns no gradient."""
 
     @staticmethod
     def forward(ctx, mod, ids, dense, packed, *params):
@@ -3221,6 +3223,11 @@ class _LinearFn(torch.autograd.Function):
         B = ids.shape[0]
         weight = params[-1].contiguous() if lay.n_dense else None
         d = _linear_desc(mod, ids, dense, packed, weight)
+        rec = getattr(mod, "_table_opt", None)
+        if rec is not None:
+            rec.check_device()
+            if rec.lazy:
+                rec.replay_linear(d)
         logit = torch.empty(B, 1, dtype=torch.float32, device=dev)
         rows = torch.empty(B, lay.R, dtype=torch.int32, device=dev)
         mask = torch.empty(B, lay.Fv, dtype=torch.int32, device=dev)
@@ -3229,6 +3236,7 @@ class _LinearFn(torch.autograd.Function):
                                        mod._status.data_ptr(), N.stream_handle(dev)), "satrans_linear_fwd")
         mod._raise_on_status("LinearModel")
         ctx.mod, ctx.packed, ctx.ids, ctx.dense = mod, packed, ids, dense
+        ctx.rec, ctx.fwd_t = rec, (rec.opt.t if rec is not None else 0)
         ctx.save_for_backward(rows, mask, argmax, *([weight] if lay.n_dense else []))
         return logit
 
@@ -3242,15 +3250,26 @@ class _LinearFn(torch.autograd.Function):
         dlogit = dlogit.contiguous().float()
         f32 = dict(dtype=torch.float32, device=dev)
         g_arena = sorted_rows = src = dweight = None
+        rec = ctx.rec
+        if rec is not None:
+            rec.refuse_second()
         if lay.F:
             sorted_rows, src = _sorted_positions(lib, rows, rows.numel(), d.arena_rows, dev)
-            g_arena = torch.zeros(d.arena_rows, 1, **f32)
+            if rec is None:
+                g_arena = torch.zeros(d.arena_rows, 1, **f32)
+            else:                                     # the optimizer's buffer: all-zero already in the lazy form (its step clears
+                g_arena = rec.g                       # the rows written here), cleared here for the dense sweep
+                if not rec.lazy:
+                    g_arena.zero_()
         if lay.n_dense:
             dweight = torch.empty(lay.n_dense, 1, **f32)
         work = torch.empty(max(256, _native_size(lib.satrans_linear_workspace_bytes, d)), dtype=torch.uint8, device=dev)
         N.check(lib.satrans_linear_bwd(C.byref(d), dlogit.data_ptr(), rows.data_ptr(), mask.data_ptr(), argmax.data_ptr(),
                                        N.ptr(sorted_rows), N.ptr(src), N.ptr(g_arena), N.ptr(dweight), work.data_ptr(),
                                        N.stream_handle(dev)), "satrans_linear_bwd")
+        if rec is not None:
+            rec.take(sorted_rows, src, dweight, rows.numel(), ctx.fwd_t)
+            return (None,) * (4 + len(mod._layout.names) * bool(lay.F) + bool(lay.n_dense))
         grads = (mod._table_grads(g_arena) if lay.F else []) + ([dweight] if lay.n_dense else [])
         return (None, None, None, None, *grads)
 
@@ -3274,10 +3293,12 @@ class LinearModel(_TableArena, _LinearTables):
     then `weight`): state_dict keys `embedding_dict.<embedding_name>.weight` [V, 1] and `weight` [n_dense, 1] (absent without a
     DenseFeat); fields sharing an embedding_name share one parameter.  The tables are views of one 1-wide arena (`self.arena`),
     rebound after `.to()`.  This is the reference's sparse=False semantics: every table receives a DENSE gradient, a slice of one
-    zero-filled [rows, 1] buffer, so any torch optimizer trains it.  Without sparse and varlen columns the result is the dense
-    term alone; without dense columns there is no `weight`; with neither, zeros [B, 1] (the reference's).
+    zero-filled [rows, 1] buffer, so any torch optimizer trains it.  Adopted by an optim.TableAdam, the backward stores the row
+    sums into a buffer the optimizer owns, every `.grad` stays None, and the optimizer steps the tables (one satrans_adam_flat
+    sweep, or the lazy 1-wide kernels with `linear_lazy=True`) and `weight`.  Without sparse and varlen columns the result is the
+    dense term alone; without dense columns there is no `weight`; with neither, zeros [B, 1] (the reference's).
     Not built: `sparse_feat_refine_weight` (IFM / DIFM; NotImplementedError - the reference never passes it), sparse-COO
-    gradients, a fused optimizer step for these tables, bf16, one sort shared with FeatureEmbedding."""
+    gradients, bf16, one sort shared with FeatureEmbedding."""
 
     def __init__(self, feature_columns, feature_index, init_std=0.0001, device='cpu'):
         lay = _FieldLayout("LinearModel", feature_columns, feature_index)      # (refuses before a generator draw is made)
@@ -3308,7 +3329,10 @@ class LinearModel(_TableArena, _LinearTables):
 class _FeatureEmbeddingFn(torch.autograd.Function):
     """emb [B, F, D] of FeatureEmbedding over the existing ABI: satrans_gather_fwd (no varlen column) or satrans_pool_gather_fwd;
     backward satrans_pool_bwd (varlen only), satrans_embed_sort, then the dense gradient into a zero-filled [rows, D] by
-    satrans_embed_segment_sums or satrans_embed_grad_dense(l2 = 0) (FeatureEmbedding.dense_gradient)."""
+    satrans_embed_segment_sums or satrans_embed_grad_dense(l2 = 0) (FeatureEmbedding.dense_gradient).
+    Adopted by an optim.TableAdam: the lazy form runs a rows-only pass, the sort and satrans_embed_lazy_replay of exactly these
+    rows in front of the gather (the sort is kept for the backward); the backward stops after the sort, hands (sorted_rows, src,
+    gemb) to the optimizer and returns no gradient - the [rows, D] buffer is never built."""
 
     @staticmethod
     def forward(ctx, mod, ids, *tables):
@@ -3319,6 +3343,20 @@ class _FeatureEmbeddingFn(torch.autograd.Function):
         rows = torch.empty(B, lay.R, dtype=torch.int32, device=dev)
         mask = argmax = None
         st = N.stream_handle(dev)
+        rec, presorted = getattr(mod, "_table_opt", None), None
+        if rec is not None:
+            rec.check_device()
+        if rec is not None and rec.lazy:      # rows only (an id outside its table counts as its first row: the replay is neutral)
+            if lay.Fv == 0:
+                N.check(lib.satrans_gather_fwd(arena.data_ptr(), mod._row_span.data_ptr(), mod._gather_cols.data_ptr(),
+                                               ids.data_ptr(), N.id_dtype_of(ids), ids.shape[1], B, lay.F, D, None, rows.data_ptr(),
+                                               mod._status.data_ptr(), st), "satrans_gather_fwd(rows)")
+            else:
+                N.check(lib.satrans_pool_gather_fwd(arena.data_ptr(), arena.shape[0], None, None, lay.fields, lay.F, lay.R, lay.Fv,
+                                                    ids.data_ptr(), N.id_dtype_of(ids), ids.shape[1], B, D, None, rows.data_ptr(),
+                                                    None, None, mod._status.data_ptr(), st), "satrans_pool_gather_fwd(rows)")
+            presorted = _sorted_positions(lib, rows, B * lay.R, arena.shape[0], dev)
+            rec.replay(presorted[0], B * lay.R)
         if lay.Fv == 0:
             N.check(lib.satrans_gather_fwd(arena.data_ptr(), mod._row_span.data_ptr(), mod._gather_cols.data_ptr(), ids.data_ptr(),
                                            N.id_dtype_of(ids), ids.shape[1], B, lay.F, D, emb.data_ptr(), rows.data_ptr(),
@@ -3332,6 +3370,7 @@ class _FeatureEmbeddingFn(torch.autograd.Function):
                     "satrans_pool_gather_fwd")
         mod._raise_on_status("FeatureEmbedding")
         ctx.mod = mod
+        ctx.rec, ctx.presorted, ctx.fwd_t = rec, presorted, (rec.opt.t if rec is not None else 0)
         ctx.save_for_backward(rows, *([mask, argmax] if lay.Fv else []))
         return emb
 
@@ -3342,13 +3381,19 @@ class _FeatureEmbeddingFn(torch.autograd.Function):
         rows, *pooled = ctx.saved_tensors
         dev, st = rows.device, N.stream_handle(rows.device)
         B, D, total = rows.shape[0], arena.shape[1], arena.shape[0]
+        rec = ctx.rec
+        if rec is not None:
+            rec.refuse_second()
         gemb = demb.contiguous().float()
         if lay.Fv:
             dx, gemb = gemb, torch.empty(B * lay.R, D, dtype=torch.float32, device=dev)
             N.check(lib.satrans_pool_bwd(dx.data_ptr(), lay.fields, lay.F, lay.R, lay.Fv, B, D, pooled[0].data_ptr(),
                                          pooled[1].data_ptr(), gemb.data_ptr(), st), "satrans_pool_bwd")
         n = B * lay.R
-        sorted_rows, src = _sorted_positions(lib, rows, n, total, dev)
+        sorted_rows, src = ctx.presorted if ctx.presorted is not None else _sorted_positions(lib, rows, n, total, dev)
+        if rec is not None:
+            rec.take(sorted_rows, src, gemb, n, ctx.fwd_t)
+            return (None,) * (2 + len(lay.names))
         g_arena = torch.zeros(total, D, dtype=torch.float32, device=dev)
         if mod.dense_gradient == "segment_sums":      # the engine's chunked ordered sums, stored instead of applied
             part = torch.empty(int(lib.satrans_embed_partial_ws_floats(n, D)), dtype=torch.float32, device=dev)
@@ -3381,12 +3426,13 @@ class FeatureEmbedding(_TableArena, nn.Module):
     This is the reference's sparse=False semantics: every table's gradient is DENSE, a slice of one zero-filled [rows, D] buffer
     in which every row exists.  At AliCCP size (about 6.6 M rows) that buffer is 0.84 GB at D = 32: it is zero-filled and
     written every backward and read again, with two moment buffers of the same size, by a dense optimizer step - against a few
-    MB of gathered rows.  The lazy, touched-rows-only Adam step of the SATrans engine is not available here; a model that needs it
-    is built behind BaseModel.
+    MB of gathered rows.  optim.TableAdam removes both: an adopted module's forward first replays the postponed steps of the
+    batch's rows (also under no_grad and in eval()), its backward hands (sorted_rows, src, gemb) to the optimizer instead of
+    building the buffer - every `.grad` stays None - and the step touches gathered rows only (profiles/table_adam_time.txt).
+    Between steps `embedding_dict[...].weight` then shows postponed rows as they were left; `state_dict()` flushes first.
     embedding_dim must be one of {16, 32, 64, 128} and the same for every field, at most POOL_MAX_FIELDS fields and
     POOL_MAX_LEN slots per list: ValueError at construction.
-    Not built: sparse-COO gradients, a fused optimizer step for these tables, bf16, one sort shared with LinearModel, baseline
-    model classes behind BaseModel."""
+    Not built: sparse-COO gradients, bf16, one sort shared with LinearModel, baseline model classes behind BaseModel."""
 
     def __init__(self, feature_columns, feature_index, init_std=0.0001, device='cpu'):
         lay = _FieldLayout("FeatureEmbedding", feature_columns, feature_index)
