@@ -47,7 +47,9 @@ extern "C" {
  *    satrans_outer_product_*, satrans_pnn_*), and FM, BiInteractionPooling, AFM and the DeepFM / NFM heads (satrans_fm_*,
  *    satrans_bipool_*, satrans_afm_*, satrans_fmhead_*), and AutoInt's interacting layer and head (satrans_interacting_*,
  *    satrans_autoint_*), and ESMM's two towers and WDL's DNN head with dropout (satrans_esmm_desc, satrans_esmm_grads,
- *    satrans_esmm_*). */
+ *    satrans_esmm_*), and the prediction + loss + gradient of a logit column (satrans_point_loss,
+ *    satrans_point_loss_partials), and the lazy replay and flush with the regulariser's sums in the step kernels'
+ *    arithmetic (satrans_embed_lazy_replay_reg64, satrans_embed_lazy_flush_reg64). */
 #define SATRANS_ABI_VERSION 7
 
 /* error codes */
@@ -1252,6 +1254,25 @@ int satrans_head_loss(const float* a, const float* dense, int64_t dense_stride, 
                       int FD, const float* w, const float* bias, float* prob, float* logit, const float* y, double* loss_sum,
                       float* da, float* g_w, float* g_b, float* scratch, int loss_kind, void* stream);
 
+/* Prediction, loss (reduction='sum') and the loss's gradient for a column of logits, for the models whose head ends in a logit
+ * (reference models/basemodel.py:299-315: `model(x).squeeze()`, `loss_func(y_pred, y, reduction='sum')`, and their backward;
+ * PredictionLayer: sigmoid for task='binary', the identity for task='regression').  The arithmetic per sample is
+ * satrans_head_loss's: at the same logit `pred` and `dz` carry the bits of its `prob` and `dlogit`.
+ *   z        logit of sample b at z[b * z_stride] (z_stride in elements: a column of a [B, T] block)
+ *   y        [B] labels, or NULL: prediction only (`dz`, `loss_sum`, `partial` are not touched)
+ *   pred     [B]
+ *   dz       [B] d(loss sum)/dz, or NULL (evaluation)
+ *   loss_sum [1] double, += the sum of the per-sample fp32 losses, each widened to double and added in a fixed order
+ *            (lane, wave, block, then the blocks in index order): two runs give the same bits; no floating-point atomics
+ *   partial  satrans_point_loss_partials(B) doubles of scratch (may be NULL when B <= 256)
+ * At most two launches.  SATRANS_PRED_LINEAR with SATRANS_LOSS_BCE takes z itself as the probability, as the reference
+ * would. */
+#define SATRANS_PRED_SIGMOID 0
+#define SATRANS_PRED_LINEAR 1
+int64_t satrans_point_loss_partials(int B);
+int satrans_point_loss(const float* z, int64_t z_stride, const float* y, int B, int pred_kind, int loss_kind, float* pred, float* dz,
+                       double* loss_sum, double* partial, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * The LAST layer of a training step with the head fused in: one launch (plus two small fixed-order reductions) that replaces
  *   satrans_layer_fwd(last layer) + satrans_head_loss + satrans_layer_bwd(last layer)
@@ -1433,6 +1454,17 @@ int satrans_embed_lazy_replay(float* arena, float* m, float* v, int32_t* last, i
 int satrans_embed_lazy_flush(float* arena, float* m, float* v, int32_t* last, int64_t total_rows, int D, int target,
                              const double* table, const satrans_adam_hparams* h, int64_t n, double* reg_partials,
                              void* stream);
+/* The same two calls with the partial sums of the regulariser in the step kernels' arithmetic: every replayed step adds
+ * l2 * p^2 with p widened to double first (as satrans_embed_adam_touched / _untouched do), where the two calls above add an
+ * element's postponed p^2 in fp32 and widen once.  arena, m, v and last come out the same bits; a caller that holds ONE total of
+ * the step and replay sums against the streaming form's (optim.TableAdam(track_regularizer=True)) uses these.  One loop per
+ * lane over the per-step table: slower than the calls above where many steps are pending. */
+int satrans_embed_lazy_replay_reg64(float* arena, float* m, float* v, int32_t* last, int D, const int32_t* sorted_rows,
+                                    int64_t n, int target, const double* table, const satrans_adam_hparams* h,
+                                    double* reg_partials, void* stream);
+int satrans_embed_lazy_flush_reg64(float* arena, float* m, float* v, int32_t* last, int64_t total_rows, int D, int target,
+                                   const double* table, const satrans_adam_hparams* h, int64_t n, double* reg_partials,
+                                   void* stream);
 int satrans_embed_lazy_mark(const int32_t* sorted_rows, int64_t n, int32_t* last, int t, void* stream);
 
 /* The lazy form for 1-wide tables (LinearModel's arena [arena_rows, 1]; additive under ABI 7): the bits of

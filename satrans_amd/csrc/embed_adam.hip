@@ -882,6 +882,94 @@ __global__ __launch_bounds__(256) void lazy_flush_kernel(float4* __restrict__ P,
     if (threadIdx.x == 0) reg_partials[blockIdx.x] = total;
 }
 
+// ---- the replay with the regulariser's value in the step kernels' arithmetic (optim.TableAdam(track_regularizer=True)) ----------
+// replay_element4 adds an element's postponed p^2 in fp32 and widens the sum once; the step kernels (adam4) widen every p before
+// they square it.  A caller that adds the two kinds of partial sums into ONE total and holds it against the streaming form's needs
+// the same terms from both: here every replayed step contributes l2 * (p.x^2 + p.y^2 + p.z^2 + p.w^2) in double, adam4's expression,
+// in front of the same adam_step4 / adam_step4_fast update (so P, M, V come out the bits of replay_element4).  One loop per lane
+// over the per-step table, as replay_element4's own table loops.  The kernels above and their entry points are untouched.
+__device__ __forceinline__ double replay_element4_reg64(float4& P4, float4& M4, float4& V4, int from, int to,
+                                                        const double2* __restrict__ table, const LazyK& k) {
+    f32x2 p[2] = {{P4.x, P4.y}, {P4.z, P4.w}}, m[2] = {{M4.x, M4.y}, {M4.z, M4.w}}, v[2] = {{V4.x, V4.y}, {V4.z, V4.w}};
+    double reg = 0.0;
+    for (int s = from + 1; s <= to; ++s) {
+        const double2 hp = table[s];
+        reg += (double)k.l2 * ((double)p[0].x * p[0].x + (double)p[0].y * p[0].y + (double)p[1].x * p[1].x + (double)p[1].y * p[1].y);
+        f32x2 sq[2] = {{0.f, 0.f}, {0.f, 0.f}};      // (the fp32 sum of the step functions: not used here)
+        if (k.fast) adam_step4_fast(p, m, v, sq, -(float)hp.x, (float)hp.y, k);
+        else adam_step4(p, m, v, sq, -(float)hp.x, hp.y, k);
+    }
+    P4 = make_float4(p[0].x, p[0].y, p[1].x, p[1].y);
+    M4 = make_float4(m[0].x, m[0].y, m[1].x, m[1].y);
+    V4 = make_float4(v[0].x, v[0].y, v[1].x, v[1].y);
+    return reg;
+}
+
+// lazy_replay_kernel with replay_element4_reg64
+template <int D>
+__global__ __launch_bounds__(256) void lazy_replay_reg64_kernel(float4* __restrict__ P, float4* __restrict__ M, float4* __restrict__ V,
+                                                               int32_t* __restrict__ last, const int32_t* __restrict__ sorted_rows,
+                                                               int64_t n, int target, const double2* __restrict__ table, LazyK k,
+                                                               double* __restrict__ reg_partials, int64_t slots) {
+    constexpr int LR = D / 4;
+    __shared__ double s_red[256];
+    const int64_t j = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LR;
+    const int c = threadIdx.x % LR;
+    int from = target;
+    int64_t at = 0;
+    if (j < n) {
+        const int32_t row = sorted_rows[j];
+        const bool head = j == 0 || sorted_rows[j - 1] != row;
+        if (head) {
+            from = min(last[row], target);
+            at = (int64_t)row * LR + c;
+        }
+    }
+    const bool work = from < target;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f), m = p, v = p;
+    if (work) { p = P[at]; m = M[at]; v = V[at]; }
+    const double reg = replay_element4_reg64(p, m, v, from, target, table, k);
+    if (work) { P[at] = p; M[at] = m; V[at] = v; }
+    // every lane of a row has read last[row] before any lane overwrites it
+    __syncthreads();
+    if (j < n && c == 0) {
+        const int32_t row = sorted_rows[j];
+        if ((j == 0 || sorted_rows[j - 1] != row) && last[row] < target) last[row] = target;
+    }
+    const double total = block_sum(reg, s_red);
+    if (threadIdx.x == 0) {
+        reg_partials[blockIdx.x] = total;
+        for (int64_t t = (int64_t)blockIdx.x + gridDim.x; t < slots; t += gridDim.x) reg_partials[t] = 0.0;
+    }
+}
+
+// lazy_flush_kernel with replay_element4_reg64
+template <int D>
+__global__ __launch_bounds__(256) void lazy_flush_reg64_kernel(float4* __restrict__ P, float4* __restrict__ M, float4* __restrict__ V,
+                                                              int32_t* __restrict__ last, int64_t total_rows, int target,
+                                                              const double2* __restrict__ table, LazyK k,
+                                                              double* __restrict__ reg_partials) {
+    constexpr int LR = D / 4;
+    __shared__ double s_red[256];
+    double reg = 0.0;
+    const int64_t groups_per_pass = (int64_t)gridDim.x * 256 / LR;
+    const int c = threadIdx.x % LR;
+    for (int64_t row = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LR; row < total_rows; row += groups_per_pass) {
+        const int from = min(last[row], target);
+        if (from < target) {
+            const int64_t at = row * LR + c;
+            float4 p = P[at], m = M[at], v = V[at];
+            reg += replay_element4_reg64(p, m, v, from, target, table, k);
+            P[at] = p; M[at] = m; V[at] = v;
+        }
+    }
+    __syncthreads();    // all reads of last[] in this block are done; blocks own disjoint rows
+    for (int64_t row = ((int64_t)blockIdx.x * 256 + threadIdx.x) / LR; row < total_rows; row += groups_per_pass)
+        if (c == 0 && last[row] < target) last[row] = target;
+    const double total = block_sum(reg, s_red);
+    if (threadIdx.x == 0) reg_partials[blockIdx.x] = total;
+}
+
 // Diagnostic behind the packed arithmetic: mode 0 compares pk_sqrt_rn with RN32(sqrt in fp64) on the floats whose bit patterns are
 // [first, first + count) (the caller walks the whole packed range), mode 1 compares pk_div_rn with RN32(fp64 quotient) on `count`
 // pseudo-random (a, b) pairs drawn from seed `first` with a in +-[2^-80, 2^40], b in [2^-30, 2^38]; mismatches are counted.
@@ -1579,6 +1667,40 @@ extern "C" int satrans_embed_lazy_flush(float* arena, float* m, float* v, int32_
     DISPATCH_D(D, (lazy_flush_kernel<DD><<<kFlushBlocks, 256, 0, stream>>>((float4*)arena, (float4*)m, (float4*)v, last, total_rows,
                                                                           target, (const double2*)table, k, reg)));
     SATRANS_CHECK_LAUNCH("lazy_flush_kernel");
+    return SATRANS_OK;
+}
+
+// The two calls above with the regulariser's partial sums in the step kernels' arithmetic (replay_element4_reg64): the same
+// arguments, the same slots, the same P, M, V and last.
+extern "C" int satrans_embed_lazy_replay_reg64(float* arena, float* m, float* v, int32_t* last, int D,
+                                               const int32_t* sorted_rows, int64_t n, int target, const double* table,
+                                               const satrans_adam_hparams* h, double* reg_partials, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SATRANS_REQUIRE(arena && m && v && last && sorted_rows && table && h && reg_partials, SATRANS_E_BADARG,
+                    "embed_lazy_replay_reg64: null pointer");
+    SATRANS_REQUIRE(n > 0 && target >= 0, SATRANS_E_BADARG, "embed_lazy_replay_reg64: n=%lld target=%d", (long long)n, target);
+    const LazyK k = make_lazyk(*h);
+    const int64_t slots = ceil_div(n * D, 256);
+    const int64_t blocks = ceil_div(n * (D / 4), 256);
+    DISPATCH_D(D, (lazy_replay_reg64_kernel<DD><<<(unsigned)blocks, 256, 0, stream>>>((float4*)arena, (float4*)m, (float4*)v, last,
+                                                                                      sorted_rows, n, target, (const double2*)table,
+                                                                                      k, reg_partials, slots)));
+    SATRANS_CHECK_LAUNCH("lazy_replay_reg64_kernel");
+    return SATRANS_OK;
+}
+
+extern "C" int satrans_embed_lazy_flush_reg64(float* arena, float* m, float* v, int32_t* last, int64_t total_rows, int D,
+                                              int target, const double* table, const satrans_adam_hparams* h, int64_t n,
+                                              double* reg_partials, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    SATRANS_REQUIRE(arena && m && v && last && table && h && reg_partials, SATRANS_E_BADARG, "embed_lazy_flush_reg64: null pointer");
+    SATRANS_REQUIRE(total_rows > 0 && target >= 0 && n >= 0, SATRANS_E_BADARG, "embed_lazy_flush_reg64: rows=%lld target=%d",
+                    (long long)total_rows, target);
+    const LazyK k = make_lazyk(*h);
+    double* reg = reg_partials + ceil_div(n * D, 256);
+    DISPATCH_D(D, (lazy_flush_reg64_kernel<DD><<<kFlushBlocks, 256, 0, stream>>>((float4*)arena, (float4*)m, (float4*)v, last,
+                                                                                total_rows, target, (const double2*)table, k, reg)));
+    SATRANS_CHECK_LAUNCH("lazy_flush_reg64_kernel");
     return SATRANS_OK;
 }
 

@@ -3465,3 +3465,77 @@ class FeatureEmbedding(_TableArena, nn.Module):
             contiguous = lay.dense_cols == list(range(lo, lo + lay.n_dense))
             dense = dense[:, lo:lo + lay.n_dense] if contiguous else dense.index_select(1, self._dense_cols_x.long())
         return emb, (dense.detach() if dense is not None else None)
+
+
+# ---- the tail of a step: prediction, loss, the loss's gradient -------------------------------------------------------------------
+PRED_KINDS = {"binary": 0, "regression": 1}                              # SATRANS_PRED_SIGMOID / SATRANS_PRED_LINEAR
+LOSS_KINDS = {"binary_crossentropy": 0, "mse": 1, "mae": 2}              # SATRANS_LOSS_*
+
+
+def _point_loss_launch(logit, y, pred_kind, loss_kind, want_dz):
+    """One satrans_point_loss call over the first column of `logit` [B] / [B, T] -> (loss_sum [] fp64 or None, pred [B, 1], dz)."""
+    lib, dev, B = N.lib(), logit.device, logit.shape[0]
+    pred = torch.empty(B, 1, dtype=torch.float32, device=dev)
+    loss = dz = part = None
+    if y is not None:
+        loss = torch.zeros((), dtype=torch.float64, device=dev)
+        part = torch.empty(max(int(lib.satrans_point_loss_partials(B)), 1), dtype=torch.float64, device=dev)
+        if want_dz:
+            dz = torch.empty(B, dtype=torch.float32, device=dev)
+    N.check(lib.satrans_point_loss(logit.data_ptr(), logit.stride(0), N.ptr(y), B, pred_kind, loss_kind, pred.data_ptr(), N.ptr(dz),
+                                   N.ptr(loss), N.ptr(part), N.stream_handle(dev)), "satrans_point_loss")
+    return loss, pred, dz
+
+
+class _PointLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logit, y, pred_kind, loss_kind):
+        want = ctx.needs_input_grad[0]
+        loss, pred, dz = _point_loss_launch(logit, y, pred_kind, loss_kind, want)
+        ctx.shape = logit.shape
+        if want:
+            ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_pred):
+        dz, = ctx.saved_tensors
+        return (grad_loss.to(torch.float32) * dz).view(ctx.shape), None, None, None
+
+
+class PointLoss(nn.Module):
+    """The tail of the sibling models' training step in one call (csrc/point_loss.hip): PredictionLayer's sigmoid (task='binary')
+    or identity ('regression'), the loss of compile() with reduction='sum' (reference models/basemodel.py:299-315), and the
+    gradient of that sum at the logit.
+
+        forward(logit [B, 1] or [B] fp32, y [B] / [B, 1] fp32) -> (loss_sum: 0-dim float64 on the device, pred [B, 1] fp32)
+        forward(logit)                                          -> (None, pred [B, 1])
+
+    The arithmetic per sample is head.hip's (`pred` and the gradient equal satrans_head_loss's prob and dlogit bit for bit); the
+    sum widens every fp32 loss to double and adds them in a fixed order: the same bits every run.  ONE autograd.Function: the
+    backward is `grad_loss * dz` with the dz the forward launch wrote (not written when the logit needs no gradient); `pred`
+    carries no gradient.  'regression' with binary_crossentropy takes the logit itself as the probability, as the reference would."""
+
+    def __init__(self, loss="binary_crossentropy", task="binary"):
+        super().__init__()
+        if task not in PRED_KINDS:
+            raise ValueError("task must be binary or regression")
+        if loss not in LOSS_KINDS:
+            raise NotImplementedError(str(loss))
+        self.loss, self.task = loss, task
+
+    def forward(self, logit, y=None):
+        N.require_gpu(logit, "PointLoss")
+        if logit.dtype != torch.float32 or logit.dim() not in (1, 2) or (logit.dim() == 2 and logit.shape[1] != 1) or logit.shape[0] < 1:
+            raise ValueError(f"PointLoss: expected a float32 logit [B, 1] or [B], got {logit.dtype} {tuple(logit.shape)}")
+        logit = logit.contiguous()
+        if y is not None:
+            if y.numel() != logit.shape[0] or y.device != logit.device:
+                raise ValueError(f"PointLoss: {logit.shape[0]} logits on {logit.device}, labels {tuple(y.shape)} on {y.device}")
+            y = y.reshape(-1).to(torch.float32).contiguous()
+        pk, lk = PRED_KINDS[self.task], LOSS_KINDS[self.loss]
+        if y is None or not torch.is_grad_enabled():
+            loss, pred, _ = _point_loss_launch(logit.detach(), y, pk, lk, False)
+            return loss, pred
+        return _PointLossFn.apply(logit, y, pk, lk)

@@ -590,6 +590,8 @@ SIGNATURES = {
                                _vp, _vp, _vp, _vp, _vp]),
 "satrans_head_loss": (C.c_int, [_vp, _vp, C.c_int64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _vp, _vp, _vp, C.c_int, _vp]),
+    "satrans_point_loss_partials": (C.c_int64, [C.c_int]),
+    "satrans_point_loss": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "satrans_optim_flat": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, _vp]),
     "satrans_adam_flat": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.POINTER(AdamHParams), _vp]),
     "satrans_adam_flat_sum": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.POINTER(AdamHParams), _vp, C.c_int64, _vp, _vp]),
@@ -626,6 +628,10 @@ SIGNATURES = {
                                             C.POINTER(AdamHParams), _vp, _vp]),
     "satrans_embed_lazy_flush": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, C.POINTER(AdamHParams),
                                            C.c_int64, _vp, _vp]),
+    "satrans_embed_lazy_replay_reg64": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, _vp, C.c_int64, C.c_int, _vp,
+                                                  C.POINTER(AdamHParams), _vp, _vp]),
+    "satrans_embed_lazy_flush_reg64": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int, C.c_int, _vp, C.POINTER(AdamHParams),
+                                                 C.c_int64, _vp, _vp]),
     "satrans_embed_lazy_mark": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, _vp]),
     "satrans_embed1_lazy_replay": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(PoolField), C.c_int, C.c_int,
                                              _vp, C.c_int, C.c_int64, C.c_int, C.c_int, _vp, C.POINTER(AdamHParams), _vp]),

@@ -27,8 +27,14 @@ bits).  `LinearModel.weight` takes satrans_adam_flat in the exact arithmetic, as
 
 The learning rate is read from `param_groups[0]["lr"]` at every step, so torch.optim.lr_scheduler works; a rate change needs
 no flush, because the replay reads each step's constants from a per-step table (`StepTable`, built as PathEngine._table builds
-its own).  betas and eps are fixed at construction.  Only the gradient of the regulariser is applied; its value is not
-computed.  Not built: gradient accumulation (a second backward before step() raises), optimizers other than Adam, several
+its own).  betas and eps are fixed at construction.  Only the gradient of the regulariser is applied; its VALUE is computed on
+request: `track_regularizer=True` adds the partial sums the touched, untouched, replay and flush kernels write (l2 * p^2 at the
+pre-step values) into one device double, one satrans_sum_f64 launch after each of them - the replay and the flush then run as
+satrans_embed_lazy_replay_reg64 / satrans_embed_lazy_flush_reg64, the same tables and moments with every replayed p^2 formed in
+double as the step kernels form it, so that the lazy and the streaming totals are the same terms in another grouping - and, for the 1-wide arena and
+`LinearModel.weight`, whose satrans_adam_flat step writes none - l2 * sum(p^2) by a torch reduction, which costs one more read
+of the 1-wide arena per step (`regularization_sum()`).  Off (the default), the optimizer runs the launches it always ran.
+Not built: gradient accumulation (a second backward before step() raises), optimizers other than Adam, several
 ranks, weight_decay / amsgrad / maximize, a second param group."""
 from __future__ import annotations
 
@@ -152,9 +158,10 @@ class _Adopted:
         D = arena.shape[1]
         h = opt.hparams(self.l2, opt.arith)
         reg = self.scratch("lazy_reg", lib.satrans_embed_lazy_reg_partials(n, D), torch.float64, zero=True)
-        N.check(lib.satrans_embed_lazy_replay(arena.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.last.data_ptr(), D,
-                                              sorted_rows.data_ptr(), n, opt.t, opt.table(self.dev).data_ptr(), C.byref(h),
-                                              reg.data_ptr(), N.stream_handle(self.dev)), "satrans_embed_lazy_replay")
+        call = lib.satrans_embed_lazy_replay_reg64 if opt.track_regularizer else lib.satrans_embed_lazy_replay
+        N.check(call(arena.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.last.data_ptr(), D, sorted_rows.data_ptr(), n, opt.t,
+                     opt.table(self.dev).data_ptr(), C.byref(h), reg.data_ptr(), N.stream_handle(self.dev)), "satrans_embed_lazy_replay")
+        opt._add_reg(reg, (n * D + 255) // 256, self.dev)      # (the slots this call wrote; the rest of the buffer is the flush's)
 
     def replay_linear(self, d) -> None:
         """LinearModel, lazy: every slot row of the batch behind the descriptor `d`, before satrans_linear_fwd reads it."""
@@ -188,7 +195,8 @@ class _Adopted:
             total, D = arena.shape
             h = opt.hparams(self.l2, opt.arith)
             part = self.scratch("partial", lib.satrans_embed_partial_ws_floats(n, D), torch.float32)
-            reg = self.scratch("reg", lib.satrans_embed_reg_partials(total, n, D), torch.float64)
+            # (tracked: zero-filled once, because the lazy form never writes the slots of the streaming kernel)
+            reg = self.scratch("reg", lib.satrans_embed_reg_partials(total, n, D), torch.float64, zero=opt.track_regularizer)
             if not opt.lazy:
                 bitmap = self.scratch("touched", (total + 31) // 32, torch.int32)
                 N.check(lib.satrans_embed_mark_touched(sorted_rows.data_ptr(), n, total, bitmap.data_ptr(), st),
@@ -200,10 +208,12 @@ class _Adopted:
                                                    src.data_ptr(), n, grad.data_ptr(), part.data_ptr(), C.byref(h), reg.data_ptr(),
                                                    self.last.data_ptr() if opt.lazy else None, t if opt.lazy else 0, st),
                     "satrans_embed_adam_touched")
+            opt._add_reg(reg, reg.numel(), self.dev)
             return
         if self.m is not None:
             arena = self.arena()
             h = opt.hparams(self.l2, opt.arith)
+            opt._add_reg_of(arena, self.l2)
             if self.lazy:
                 N.check(lib.satrans_embed1_adam_rows(arena.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.last.data_ptr(),
                                                      self.g.data_ptr(), arena.shape[0], sorted_rows.data_ptr(), n, C.byref(h), t, st),
@@ -214,6 +224,7 @@ class _Adopted:
         if self.wm is not None:
             w = self.mod.weight.data
             h = opt.hparams(self.l2, "exact")
+            opt._add_reg_of(w, self.l2)
             N.check(lib.satrans_adam_flat(N.ptr(w), grad.data_ptr(), self.wm.data_ptr(), self.wv.data_ptr(), w.numel(), C.byref(h),
                                           st), "satrans_adam_flat")
 
@@ -226,9 +237,10 @@ class _Adopted:
         table = opt.table(self.dev)
         if self.kind == "embedding":
             reg = self.scratch("flush_reg", 4096, torch.float64)
-            N.check(lib.satrans_embed_lazy_flush(arena.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.last.data_ptr(),
-                                                 arena.shape[0], arena.shape[1], t, table.data_ptr(), C.byref(h), 0, reg.data_ptr(),
-                                                 st), "satrans_embed_lazy_flush")
+            call = lib.satrans_embed_lazy_flush_reg64 if opt.track_regularizer else lib.satrans_embed_lazy_flush
+            N.check(call(arena.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.last.data_ptr(), arena.shape[0], arena.shape[1],
+                         t, table.data_ptr(), C.byref(h), 0, reg.data_ptr(), st), "satrans_embed_lazy_flush")
+            opt._add_reg(reg, reg.numel(), self.dev)
         else:
             N.check(lib.satrans_embed1_lazy_flush(arena.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), self.last.data_ptr(),
                                                   arena.shape[0], t, table.data_ptr(), C.byref(h), st), "satrans_embed1_lazy_flush")
@@ -255,7 +267,8 @@ class TableAdam(torch.optim.Optimizer):
     `load_state_dict` takes it back (every row then stands at `step`)."""
 
     def __init__(self, modules, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, l2_reg_embedding=1e-5, l2_reg_linear=1e-5, arith="fast",
-                 lazy=True, flush_every=32, linear_lazy=False, weight_decay=0, amsgrad=False, maximize=False):
+                 lazy=True, flush_every=32, linear_lazy=False, weight_decay=0, amsgrad=False, maximize=False,
+                 track_regularizer=False):
         from .layers import FeatureEmbedding, LinearModel
         for name, val in (("weight_decay", weight_decay), ("amsgrad", amsgrad), ("maximize", maximize)):
             if val:
@@ -275,7 +288,12 @@ class TableAdam(torch.optim.Optimizer):
         for i, mod in enumerate(modules):
             if getattr(mod, "_table_opt", None) is not None or any(mod is other for other in modules[:i]):
                 raise ValueError(f"TableAdam: this {type(mod).__name__} is already adopted by a TableAdam (one optimizer per module)")
+        if track_regularizer and linear_lazy:
+            raise NotImplementedError("TableAdam: track_regularizer with linear_lazy=True (the lazy 1-wide kernels write no partial "
+                                      "sums of the regulariser, and a postponed row is not at its pre-step value)")
         self.arith, self.lazy, self.linear_lazy = arith, bool(lazy), bool(linear_lazy)
+        self.track_regularizer = bool(track_regularizer)
+        self._reg_sum = {}               # device -> [1] fp64
         self.flush_every = int(flush_every) if flush_every else 0
         self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
         self.t = 0                       # completed steps
@@ -311,6 +329,42 @@ class TableAdam(torch.optim.Optimizer):
 
     def table(self, dev) -> torch.Tensor:
         return self._steps.device(self.t, dev)
+
+    # ---- the regulariser's value ------------------------------------------------------------------------------------------------
+    def _reg_total(self, dev) -> torch.Tensor:
+        if dev not in self._reg_sum:
+            self._reg_sum[dev] = torch.zeros(1, dtype=torch.float64, device=dev)
+        return self._reg_sum[dev]
+
+    def _add_reg(self, partials, count: int, dev) -> None:
+        """total += the first `count` partial sums a step, replay or flush kernel has just written (one launch, index order)."""
+        if self.track_regularizer:
+            N.check(N.lib().satrans_sum_f64(partials.data_ptr(), int(count), self._reg_total(dev).data_ptr(), 1, N.stream_handle(dev)),
+                    "satrans_sum_f64")
+
+    def _add_reg_of(self, p, l2: float) -> None:
+        """total += l2 * sum(p^2) of a buffer that steps by satrans_adam_flat, which writes no partial sums: a torch reduction over
+        its pre-step values, in double."""
+        if self.track_regularizer and l2 != 0.0:
+            self._reg_total(p.device).add_(l2 * torch.sum(torch.square(p.detach().double())))
+
+    def regularization_sum(self) -> torch.Tensor:
+        """The running total of the regulariser's VALUE, l2 * sum(p^2) over the adopted tables (and LinearModel.weight) at the
+        pre-step values of every step taken, as a 0-dim float64 tensor on the modules' device - what the reference adds to each
+        step's loss (`get_regularization_loss` at loss time), summed over the steps.  Needs `track_regularizer=True`.  Never
+        synchronises.  In the lazy form a row's postponed steps enter the total when they are replayed, so the total equals the
+        streaming form's only after `flush()`.  `zero_regularization_sum()` starts a new total (an epoch's)."""
+        if not self.track_regularizer:
+            raise RuntimeError("TableAdam.regularization_sum: the optimizer was built with track_regularizer=False")
+        parts = [self._reg_total(dev) for dev in dict.fromkeys(rec.dev for rec in self._adopted)]
+        total = parts[0][0].clone()
+        for part in parts[1:]:
+            total = total + part[0].to(total.device)
+        return total
+
+    def zero_regularization_sum(self) -> None:
+        for t in self._reg_sum.values():
+            t.zero_()
 
     # ---- the step --------------------------------------------------------------------------------------------------------------
     def _drop_all(self) -> None:
