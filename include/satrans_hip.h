@@ -48,7 +48,7 @@ extern "C" {
  *    satrans_bipool_*, satrans_afm_*, satrans_fmhead_*), and AutoInt's interacting layer and head (satrans_interacting_*,
  *    satrans_autoint_*), and ESMM's two towers and WDL's DNN head with dropout (satrans_esmm_desc, satrans_esmm_grads,
  *    satrans_esmm_*), and the prediction + loss + gradient of a logit column (satrans_point_loss,
- *    satrans_point_loss_partials), and the lazy replay and flush with the regulariser's sums in the step kernels'
+ *    satrans_point_loss_partials) and its routed form over a [B, T] block (satrans_point_loss_routed), and the lazy replay and flush with the regulariser's sums in the step kernels'
  *    arithmetic (satrans_embed_lazy_replay_reg64, satrans_embed_lazy_flush_reg64). */
 #define SATRANS_ABI_VERSION 7
 
@@ -1272,6 +1272,20 @@ int satrans_head_loss(const float* a, const float* dense, int64_t dense_stride, 
 int64_t satrans_point_loss_partials(int B);
 int satrans_point_loss(const float* z, int64_t z_stride, const float* y, int B, int pred_kind, int loss_kind, float* pred, float* dz,
                        double* loss_sum, double* partial, void* stream);
+
+/* The routed form, for a [B, T] block of per-task predictions where a row's loss is taken on the column of its own task
+ * (reference models/mtl_basemodel.py:268-269, the masked per-task loss sum; :376-378, predict's assembly).  Additive in ABI
+ * version 7: a new symbol only.
+ *   z        [B, T], row b at z + b * z_stride (z_stride >= T, in elements)
+ *   task     [B] int32: the column of row b (scenario id minus domain_id_offset)
+ *   T        a runtime value, any T >= 1
+ *   dz       [B, T] contiguous, or NULL; EVERY entry is written (no zero-fill by the caller): dz[b, task[b]] = the gradient,
+ *            0 elsewhere
+ * A row with 0 <= task[b] < T computes satrans_point_loss's expressions on z[b, task[b]]: the same bits.  Any other row belongs
+ * to no task's mask, as in the reference: pred[b] = 0, nothing added to the sum, a zero dz row.  y, pred, loss_sum, partial
+ * (satrans_point_loss_partials(B)), the order of the sum and the launch count are satrans_point_loss's. */
+int satrans_point_loss_routed(const float* z, int64_t z_stride, const int32_t* task, const float* y, int B, int T, int pred_kind,
+                              int loss_kind, float* pred, float* dz, double* loss_sum, double* partial, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The LAST layer of a training step with the head fused in: one launch (plus two small fixed-order reductions) that replaces

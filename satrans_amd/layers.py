@@ -1865,7 +1865,7 @@ class FiBiNETHead(nn.Module):
     regularization_loss() -> [1] is what FiBiNET.__init__ itself adds to the reference's regularization_weight: nothing.
     The reference's fibinet.py has no add_regularization_weight call (the recorded runs pin that), so the result is zero;
     `l2_reg_linear` is accepted as the reference's constructor accepts it, where it reaches BaseModel's linear model only.
-    Not built: a FiBiNET model class behind BaseModel; dropout, batch-norm and activations other than relu in the DNN
+    Not built: dropout, batch-norm and activations other than relu in the DNN
     (NotImplementedError); bf16; more than MMOE_MAX_HIDDEN hidden layers, FIBINET_MAX_FIELDS fields, an embedding size beyond
     FIBINET_MAX_DIM (NotImplementedError at construction)."""
 
@@ -2150,7 +2150,7 @@ class PNNHead(nn.Module):
     regularization_loss() -> [1] is what PNN.__init__ itself adds to the reference's regularization_weight (pnn.py:74-76):
     l2_reg_dnn times the sum of squares of the DNN's weights (not biases) and of dnn_linear.weight, in
     get_regularization_loss's arithmetic.
-    Not built: a PNN model class behind BaseModel; dropout and activations other than relu in the DNN (NotImplementedError);
+    Not built: dropout and activations other than relu in the DNN (NotImplementedError);
     bf16; more than MMOE_MAX_HIDDEN hidden layers, PNN_MAX_FIELDS fields, an embedding size beyond PNN_MAX_DIM
     (NotImplementedError at construction)."""
 
@@ -2810,7 +2810,7 @@ class AutoIntHead(nn.Module):
     a layer can be driven alone, and a layer's `capture_attention` makes the head fill its `normalized_att_scores`.
     state_dict keys and their order are the reference's: out.bias (zeros), dnn_linear.weight (torch's default draw, bias-free),
     dnn.linears.{l}.{weight,bias} (weights N(0, init_std)), int_layers.{i}.W_Query / W_key / W_Value / W_Res.
-    att_layer_num < 1: ValueError.  Not built: an AutoInt model class behind BaseModel; dropout, batch-norm and activations
+    att_layer_num < 1: ValueError.  Not built: dropout, batch-norm and activations
     other than relu in the DNN (NotImplementedError); l2_reg_dnn; bf16; more than AUTOINT_MAX_LAYERS interacting or
     MMOE_MAX_HIDDEN hidden layers (NotImplementedError); shapes outside InteractingLayer's raise NativeError at the call."""
 
@@ -2990,8 +2990,7 @@ class ESMMHead(_DropoutDNNHead):
     Parameter names, state_dict order and initialisation are the reference ESMM's: out.bias (zeros), ctr_dnn.linears.{l}.*,
     cvr_dnn.linears.{l}.* (weights N(0, init_std)), ctr_dnn_final_layer.weight, cvr_dnn_final_layer.weight - those entries of a
     reference checkpoint load with load_state_dict.  regularization_loss() -> [1] is what ESMM.__init__ registers (esmm.py:71-76).
-    Not built: batch-norm and activations other than relu (NotImplementedError), more than MMOE_MAX_HIDDEN hidden layers, bf16,
-    an ESMM model class behind BaseModel.  Empty hidden units: ValueError (the reference indexes [-1])."""
+    Not built: batch-norm and activations other than relu (NotImplementedError), more than MMOE_MAX_HIDDEN hidden layers, bf16.  Empty hidden units: ValueError (the reference indexes [-1])."""
 
     def __init__(self, inputs_dim, tower_dnn_hidden_units=(256, 128), l2_reg_dnn=0, init_std=0.0001, dnn_dropout=0,
                  dnn_activation='relu', dnn_use_bn=False):
@@ -3539,3 +3538,79 @@ class PointLoss(nn.Module):
             loss, pred, _ = _point_loss_launch(logit.detach(), y, pk, lk, False)
             return loss, pred
         return _PointLossFn.apply(logit, y, pk, lk)
+
+
+def _routed_loss_launch(z, task, y, pred_kind, loss_kind, want_dz):
+    """One satrans_point_loss_routed call over z [B, T] -> (loss_sum [] fp64 or None, pred [B, 1], dz [B, T] or None)."""
+    lib, dev, (B, T) = N.lib(), z.device, z.shape
+    pred = torch.empty(B, 1, dtype=torch.float32, device=dev)
+    loss = dz = part = None
+    if y is not None:
+        loss = torch.zeros((), dtype=torch.float64, device=dev)
+        part = torch.empty(max(int(lib.satrans_point_loss_partials(B)), 1), dtype=torch.float64, device=dev)
+        if want_dz:
+            dz = torch.empty(B, T, dtype=torch.float32, device=dev)      # (the kernel writes every entry)
+    N.check(lib.satrans_point_loss_routed(z.data_ptr(), z.stride(0), task.data_ptr(), N.ptr(y), B, T, pred_kind, loss_kind,
+                                          pred.data_ptr(), N.ptr(dz), N.ptr(loss), N.ptr(part), N.stream_handle(dev)),
+            "satrans_point_loss_routed")
+    return loss, pred, dz
+
+
+class _RoutedPointLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, task, y, pred_kind, loss_kind):
+        want = ctx.needs_input_grad[0]
+        loss, pred, dz = _routed_loss_launch(z, task, y, pred_kind, loss_kind, want)
+        if want:
+            ctx.save_for_backward(dz)
+        ctx.mark_non_differentiable(pred)
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_pred):
+        dz, = ctx.saved_tensors
+        return grad_loss.to(torch.float32) * dz, None, None, None, None
+
+
+class RoutedPointLoss(nn.Module):
+    """PointLoss over a [B, T] block of per-task outputs, each row on the column of its own task (csrc/point_loss.hip,
+    satrans_point_loss_routed): the multi-task models' masked per-task loss sum (reference models/mtl_basemodel.py:268-269) and
+    their predict assembly (:376-378) in one launch plus the fixed-order reduction.
+
+        forward(z [B, T] fp32, task_ids [B] integer, y [B] / [B, 1] fp32) -> (loss_sum: 0-dim float64 on the device, pred [B, 1])
+        forward(z, task_ids)                                              -> (None, pred [B, 1])
+
+    `task_ids` are columns (scenario id minus domain_id_offset).  A row whose task lies in [0, T) carries PointLoss's bits for
+    z[b, task]: pred, the gradient at dz[b, task], its term of the sum.  Any other row belongs to no task, as in the reference:
+    pred 0, no loss, no gradient.  ONE autograd.Function: the backward is `grad_loss * dz` with the [B, T] dz the forward launch
+    wrote in full.  z may have any row stride (unit column stride); `pred` carries no gradient.  For a head that returns
+    probabilities (ESMMHead) take task='regression'."""
+
+    def __init__(self, loss="binary_crossentropy", task="binary"):
+        super().__init__()
+        if task not in PRED_KINDS:
+            raise ValueError("task must be binary or regression")
+        if loss not in LOSS_KINDS:
+            raise NotImplementedError(str(loss))
+        self.loss, self.task = loss, task
+
+    def forward(self, z, task_ids, y=None):
+        N.require_gpu(z, "RoutedPointLoss")
+        if z.dtype != torch.float32 or z.dim() != 2 or z.shape[0] < 1 or z.shape[1] < 1:
+            raise ValueError(f"RoutedPointLoss: expected float32 z [B, T], got {z.dtype} {tuple(z.shape)}")
+        B = z.shape[0]
+        if z.stride(1) != 1 or z.stride(0) < z.shape[1]:
+            z = z.contiguous()
+        if task_ids.numel() != B or task_ids.device != z.device or task_ids.is_floating_point():
+            raise ValueError(f"RoutedPointLoss: {B} rows on {z.device}, task ids {task_ids.dtype} {tuple(task_ids.shape)} on "
+                             f"{task_ids.device}")
+        task_ids = task_ids.reshape(-1).to(torch.int32).contiguous()
+        if y is not None:
+            if y.numel() != B or y.device != z.device:
+                raise ValueError(f"RoutedPointLoss: {B} rows on {z.device}, labels {tuple(y.shape)} on {y.device}")
+            y = y.reshape(-1).to(torch.float32).contiguous()
+        pk, lk = PRED_KINDS[self.task], LOSS_KINDS[self.loss]
+        if y is None or not torch.is_grad_enabled():
+            loss, pred, _ = _routed_loss_launch(z.detach(), task_ids, y, pk, lk, False)
+            return loss, pred
+        return _RoutedPointLossFn.apply(z, task_ids, y, pk, lk)

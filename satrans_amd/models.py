@@ -18,9 +18,11 @@ state_dict() carries the reference's keys in the reference's order (`embedding_d
 own), so a reference checkpoint loads; entries of the reference's unused meta modules (`domain_embeddings.*`, `domain_map_dnn.*`,
 `meta_net.*`, created whenever `domain_column` is given) are skipped on load and absent on save.
 
-Built: WDL, DeepFM, DCN, MMOE, Star_Net (as main.py builds it: use_domain_dnn=True, domain_id_as_feature=True).  Not built:
-the other nine model classes, a `flag` containing metatrans / usetrans / nofm / nodnn, valid_cnt_per_epoch > 1, `gpus`, bf16,
-sample weights."""
+Built: every non-SATrans branch of main.py:211-281 - WDL, DCN, DeepFM, xDeepFM, NFM, AutoInt, AFM, FiBiNET, PNN, AdaSparse;
+SharedBottom, MMOE, PLE, ESMM; Star_Net (as main.py builds it: use_domain_dnn=True, domain_id_as_feature=True).  ESMM's head ends
+in two probabilities, not one logit: it replaces `_loss_and_pred` and takes its loss by RoutedPointLoss.  Not built: a `flag`
+containing metatrans / usemetatrans / usetrans / nofm / nodnn, valid_cnt_per_epoch > 1, `gpus`, bf16, sample weights, unequal
+per-task losses."""
 from __future__ import annotations
 
 import time
@@ -35,7 +37,9 @@ from . import device_metrics as DM
 from .basemodel import BaseModel
 from .callbacks import CallbackList, History
 from .inputs import PackedInput, build_input_features
-from .layers import (DCNHead, DeepFMHead, FeatureEmbedding, LinearModel, MMoEHead, PointLoss, StarHead, WDLHead, _OutBias)
+from .layers import (AdaSparseHead, AFMHead, AutoIntHead, DCNHead, DeepFMHead, ESMMHead, FeatureEmbedding, FiBiNETHead, LinearModel,
+                     MMoEHead, NFMHead, PLEHead, PNNHead, PointLoss, RoutedPointLoss, SharedBottomHead, StarHead, WDLHead, XDeepFMHead,
+                     _OutBias)
 from .optim import TableAdam
 
 _META_PREFIXES = ("domain_embeddings.", "domain_map_dnn.", "meta_net.")
@@ -50,7 +54,8 @@ def _refuse_flag(flag, words):
 
 
 class HeadModel(nn.Module):
-    """See the module docstring.  Subclasses set `self.head` (and call `_finish()`), and implement `_logit(X)` -> [B, 1]."""
+    """See the module docstring.  Subclasses set `self.head` (and call `_finish()`), and implement `_logit(X)` -> [B, 1] (or
+    replace `_loss_and_pred`)."""
 
     # the readers the SATrans BaseModel already has: plain functions of (self, ...) over feature_index / dnn_feature_columns / device
     _pack = BaseModel._pack
@@ -107,9 +112,14 @@ class HeadModel(nn.Module):
     def _logit(self, X):
         raise NotImplementedError
 
+    def _loss_and_pred(self, X, y=None):
+        """The tail of the forward, which train_step and forward both go through -> (loss sum or None, pred [B, 1]).  A model
+        whose head does not end in one logit column (ESMM) replaces it."""
+        return self._point(self._logit(X), y)
+
     def forward(self, X):
         """The reference's forward: the prediction [B, 1] (the multi-task models: each row's own task)."""
-        return self._point(self._logit(X))[1]
+        return self._loss_and_pred(X)[1]
 
     def regularization_loss(self):
         """What the torch side of the step adds to the loss: the head's own regulariser, and that of a linear_model outside the
@@ -221,8 +231,7 @@ class HeadModel(nn.Module):
     # ---- fit ---------------------------------------------------------------------------------------------------------------------
     def train_step(self, Xb, yb):
         """One step on a device batch -> (the step's total as the torch side sees it: [1] fp64 on the device, pred [B, 1])."""
-        logit = self._logit(Xb)
-        loss, pred = self._point(logit, yb)
+        loss, pred = self._loss_and_pred(Xb, yb)
         total = loss + self.regularization_loss() + self.aux_loss
         self._dense_opt.zero_grad(set_to_none=True)
         total.backward()
@@ -487,3 +496,271 @@ class Star_Net(_ScenarioModel):
         if hasattr(sd, "_metadata"):
             out._metadata = sd._metadata
         return out
+
+
+# ---- the ten further siblings: the same recipe over the remaining heads ----------------------------------------------------------
+_TRANS_WORDS = ("usemetatrans", "metatrans", "usetrans")      # MetaNet / attention in front of the head: not built here
+
+
+def _refuse_options(what, **pairs):
+    """`name=(value, the only value served)`: NotImplementedError naming the first option that differs."""
+    for name, (val, served) in pairs.items():
+        if val != served:
+            raise NotImplementedError(f"{what}: {name}={val!r} is not built")
+
+
+def _check_tasks(what, flag, task_types, task_names, domain_column):
+    """MMOE's checks, for the models behind mtl_basemodel.py with one task per scenario."""
+    _refuse_flag(flag, _TRANS_WORDS)
+    if len(task_types) != len(task_names):
+        raise ValueError("num_tasks must be equal to the length of task_types")
+    for task_type in task_types:
+        if task_type not in ('binary', 'regression'):
+            raise ValueError("task must be binary or regression, {} is illegal".format(task_type))
+    if len(set(task_types)) > 1:
+        raise NotImplementedError(f"task_types {list(task_types)}: every task takes the same type")
+    if domain_column is None:
+        raise ValueError(f"{what}: domain_column names the column whose id picks a row's task")
+
+
+class xDeepFM(HeadModel):
+    """models/xdeepfm.py: logit = linear_model(X) + cin_linear(cin(emb)) + dnn_linear(dnn(dnn_input))."""
+
+    def __init__(self, linear_feature_columns, dnn_feature_columns, dnn_hidden_units=(256, 256), cin_layer_size=(256, 128,),
+                 cin_split_half=True, cin_activation='relu', l2_reg_linear=0.00001, l2_reg_embedding=0.00001, l2_reg_dnn=0,
+                 l2_reg_cin=0, init_std=0.0001, seed=1024, dnn_dropout=0, dnn_activation='relu', dnn_use_bn=False, task='binary',
+                 device='cpu', gpus=None, flag=None, domain_column=None, num_domains=None, meta_dnn_hidden_units=(32, 64, 32)):
+        _refuse_flag(flag, _TRANS_WORDS)
+        _refuse_options("XDeepFMHead", cin_activation=(cin_activation, 'relu'), l2_reg_dnn=(l2_reg_dnn, 0), l2_reg_cin=(l2_reg_cin, 0),
+                        dnn_dropout=(dnn_dropout, 0), dnn_activation=(dnn_activation, 'relu'), dnn_use_bn=(dnn_use_bn, False))
+        super().__init__(linear_feature_columns, dnn_feature_columns, l2_reg_linear, l2_reg_embedding, init_std, seed, task, device,
+                         gpus, flag, domain_column, num_domains)
+        self.head = XDeepFMHead(_field_count(dnn_feature_columns), self.embedding.embedding_size, _dense_dim(dnn_feature_columns),
+                                dnn_hidden_units, cin_layer_size, cin_split_half, init_std)
+        self._finish()
+
+    def _logit(self, X):
+        emb, dense = self._inputs(X)
+        return self.head(emb, dense, self.linear_model(X))
+
+
+class NFM(HeadModel):
+    """models/nfm.py: logit = linear_model(X) + dnn_linear(dnn(cat(BiInteractionPooling(emb), dense)))."""
+
+    def __init__(self, linear_feature_columns, dnn_feature_columns, dnn_hidden_units=(128, 128), l2_reg_embedding=1e-5,
+                 l2_reg_linear=1e-5, l2_reg_dnn=0, init_std=0.0001, seed=1024, bi_dropout=0, dnn_dropout=0, dnn_activation='relu',
+                 task='binary', device='cpu', gpus=None, flag=None, domain_column=None, num_domains=None,
+                 meta_dnn_hidden_units=(32, 64, 32)):
+        _refuse_flag(flag, _TRANS_WORDS)
+        super().__init__(linear_feature_columns, dnn_feature_columns, l2_reg_linear, l2_reg_embedding, init_std, seed, task, device,
+                         gpus, flag, domain_column, num_domains)
+        # (NFMHead itself refuses bi_dropout, dnn_dropout and an activation other than relu)
+        self.head = NFMHead(self.embedding.embedding_size, _dense_dim(dnn_feature_columns), dnn_hidden_units, l2_reg_dnn, init_std,
+                            bi_dropout, dnn_dropout, dnn_activation)
+        self._finish()
+
+    def _logit(self, X):
+        emb, dense = self._inputs(X)
+        return self.head(emb, dense, self.linear_model(X))
+
+
+class AFM(HeadModel):
+    """models/afm.py: logit = linear_model(X) + AFMLayer(emb); with use_attention=False the FM term in its place (DeepFMHead
+    without a DNN).  Dense columns reach the linear term only, as in the reference."""
+
+    def __init__(self, linear_feature_columns, dnn_feature_columns, use_attention=True, attention_factor=8, l2_reg_linear=1e-5,
+                 l2_reg_embedding=1e-5, l2_reg_att=1e-5, afm_dropout=0, init_std=0.0001, seed=1024, task='binary', device='cpu',
+                 gpus=None, flag=None, domain_column=None, num_domains=None, meta_dnn_hidden_units=(32, 64, 32)):
+        _refuse_flag(flag, _TRANS_WORDS)
+        super().__init__(linear_feature_columns, dnn_feature_columns, l2_reg_linear, l2_reg_embedding, init_std, seed, task, device,
+                         gpus, flag, domain_column, num_domains)
+        self.use_attention = bool(use_attention)
+        if self.use_attention:
+            self.head = AFMHead(self.embedding.embedding_size, attention_factor, l2_reg_att, afm_dropout)
+        else:
+            self.head = DeepFMHead(_field_count(dnn_feature_columns), self.embedding.embedding_size, 0, True, (), 0, init_std)
+        self._finish()
+
+    def _logit(self, X):
+        emb, _ = self._inputs(X)
+        if self.use_attention:
+            return self.head(emb, self.linear_model(X))
+        return self.head(emb, None, self.linear_model(X))
+
+
+class AutoInt(HeadModel):
+    """models/autoint.py: logit = dnn_linear(cat(int_layers(emb), dnn(dnn_input))).  As in the reference (autoint.py:46, :89-90)
+    `linear_model` exists with l2 0 and stays out of the logit."""
+
+    def __init__(self, linear_feature_columns, dnn_feature_columns, att_layer_num=3, att_head_num=2, att_res=True,
+                 dnn_hidden_units=(256, 128), dnn_activation='relu', l2_reg_dnn=0, l2_reg_embedding=1e-5, dnn_use_bn=False,
+                 dnn_dropout=0, init_std=0.0001, seed=1024, task='binary', device='cpu', gpus=None, flag=None, domain_column=None,
+                 num_domains=None, meta_dnn_hidden_units=(32, 64, 32)):
+        _refuse_flag(flag, _TRANS_WORDS)
+        _refuse_options("AutoIntHead", l2_reg_dnn=(l2_reg_dnn, 0))
+        super().__init__(linear_feature_columns, dnn_feature_columns, 0, l2_reg_embedding, init_std, seed, task, device, gpus, flag,
+                         domain_column, num_domains, linear_in_forward=False)
+        self.head = AutoIntHead(_field_count(dnn_feature_columns), self.embedding.embedding_size, _dense_dim(dnn_feature_columns),
+                                att_layer_num, att_head_num, att_res, dnn_hidden_units, init_std, dnn_dropout, dnn_activation, dnn_use_bn)
+        self._finish()
+
+    def _logit(self, X):
+        emb, dense = self._inputs(X)
+        return self.head(emb, dense)
+
+
+class FiBiNET(HeadModel):
+    """models/fibinet.py: logit = linear_model(X) + dnn_linear(dnn(cat(Bilinear(SE(emb)), Bilinear(emb), dense))).  The
+    reference registers no regulariser of its own (`l2_reg_dnn` reaches nothing there, and nothing here)."""
+
+    def __init__(self, linear_feature_columns, dnn_feature_columns, bilinear_type='interaction', reduction_ratio=3,
+                 dnn_hidden_units=(128, 128), l2_reg_linear=1e-5, l2_reg_embedding=1e-5, l2_reg_dnn=0, init_std=0.0001, seed=1024,
+                 dnn_dropout=0, dnn_activation='relu', task='binary', device='cpu', gpus=None, flag=None, domain_column=None,
+                 num_domains=None, meta_dnn_hidden_units=(32, 64, 32)):
+        _refuse_flag(flag, _TRANS_WORDS)
+        super().__init__(linear_feature_columns, dnn_feature_columns, l2_reg_linear, l2_reg_embedding, init_std, seed, task, device,
+                         gpus, flag, domain_column, num_domains)
+        self.head = FiBiNETHead(_field_count(dnn_feature_columns), self.embedding.embedding_size, _dense_dim(dnn_feature_columns),
+                                bilinear_type, reduction_ratio, dnn_hidden_units, l2_reg_linear, init_std, dnn_dropout, dnn_activation)
+        self._finish()
+
+    def _logit(self, X):
+        emb, dense = self._inputs(X)
+        # (fibinet.py:118-121: without linear columns the logit is the DNN's alone)
+        return self.head(emb, dense, self.linear_model(X) if self.linear_feature_columns else None)
+
+
+class PNN(HeadModel):
+    """models/pnn.py: logit = dnn_linear(dnn(cat(flatten(emb), inner products, outer products, dense))).  No linear columns."""
+
+    def __init__(self, dnn_feature_columns, dnn_hidden_units=(128, 128), l2_reg_embedding=1e-5, l2_reg_dnn=0, init_std=0.0001,
+                 seed=1024, dnn_dropout=0, dnn_activation='relu', use_inner=True, use_outter=False, kernel_type='mat', task='binary',
+                 device='cpu', gpus=None, flag=None, domain_column=None, num_domains=None, meta_dnn_hidden_units=(32, 64, 32)):
+        _refuse_flag(flag, _TRANS_WORDS)
+        if kernel_type not in ('mat', 'vec', 'num'):
+            raise ValueError("kernel_type must be mat,vec or num")
+        super().__init__([], dnn_feature_columns, 0, l2_reg_embedding, init_std, seed, task, device, gpus, flag, domain_column,
+                         num_domains, linear_in_forward=False)
+        self.head = PNNHead(_field_count(dnn_feature_columns), self.embedding.embedding_size, _dense_dim(dnn_feature_columns),
+                            dnn_hidden_units, use_inner, use_outter, kernel_type, l2_reg_dnn, init_std, dnn_dropout, dnn_activation)
+        self._finish()
+
+    def _logit(self, X):
+        emb, dense = self._inputs(X)
+        return self.head(emb, dense)
+
+
+class AdaSparse(HeadModel):
+    """models/adasparse.py: logit = dnn_linear(pruned_dnn(dnn_input, domain_emb)), where domain_emb is the scenario column's own
+    field of the looked-up embeddings (adasparse.py:166-167): a slice of `emb`, so autograd adds both gradient paths back into
+    the table.  `linear_model` exists, is regularised and stays out of the logit.  The reference builds its base class without
+    `domain_column` (:135-137), so it has no meta modules; nothing here has either."""
+
+    def __init__(self, linear_feature_columns, dnn_feature_columns, dnn_hidden_units=(256, 128), l2_reg_linear=1e-5,
+                 l2_reg_embedding=1e-5, l2_reg_dnn=0, init_std=0.0001, seed=1024, dnn_dropout=0, dnn_activation='relu',
+                 dnn_use_bn=False, task='binary', device='cpu', gpus=None, flag=None, domain_column=None, num_domains=None,
+                 domain_emb_dim=32):
+        _refuse_flag(flag, _TRANS_WORDS)
+        _refuse_options("AdaSparseHead", l2_reg_dnn=(l2_reg_dnn, 0))
+        if domain_column is None:
+            raise ValueError("AdaSparse: domain_column names the column whose embedding steers the pruners")
+        super().__init__(linear_feature_columns, dnn_feature_columns, l2_reg_linear, l2_reg_embedding, init_std, seed, task, device,
+                         gpus, flag, domain_column, num_domains, linear_in_forward=False)
+        from .inputs import split_columns
+        sparse = [c.name for c in split_columns(self.dnn_feature_columns)[0]]
+        if domain_column not in sparse:
+            raise ValueError(f"AdaSparse: domain_column {domain_column!r} is no sparse column of dnn_feature_columns")
+        if domain_emb_dim != self.embedding.embedding_size:
+            raise ValueError(f"AdaSparse: domain_emb_dim {domain_emb_dim} must equal the embedding width "
+                             f"{self.embedding.embedding_size}: domain_emb is the scenario column's own embedding")
+        self._domain_field = sparse.index(domain_column)
+        inputs_dim = _field_count(dnn_feature_columns) * self.embedding.embedding_size + _dense_dim(dnn_feature_columns)
+        self.head = AdaSparseHead(inputs_dim, dnn_hidden_units, domain_emb_dim, init_std, dnn_activation, dnn_dropout, dnn_use_bn)
+        self._finish()
+
+    def _logit(self, X):
+        emb, dense = self._inputs(X)
+        flat = emb.flatten(1)
+        return self.head(flat if dense is None else torch.cat([flat, dense], dim=1), emb[:, self._domain_field, :])
+
+
+class SharedBottom(_ScenarioModel):
+    """models/sharedbottom.py behind models/mtl_basemodel.py, one task per scenario, as MMOE: SharedBottomHead returns each row's
+    own task logit.  predict -> [n]."""
+    returns_column = False
+
+    def __init__(self, dnn_feature_columns, bottom_dnn_hidden_units=(256, 128), tower_dnn_hidden_units=(64,), l2_reg_linear=0.00001,
+                 l2_reg_embedding=0.00001, l2_reg_dnn=0, init_std=0.0001, seed=1024, dnn_dropout=0, dnn_activation='relu',
+                 dnn_use_bn=False, task_types=('binary', 'binary'), task_names=('ctr', 'ctcvr'), device='cpu', gpus=None,
+                 domain_column=None, flag=None):
+        _check_tasks("SharedBottom", flag, task_types, task_names, domain_column)
+        _refuse_options("SharedBottomHead", l2_reg_dnn=(l2_reg_dnn, 0))
+        super().__init__([], dnn_feature_columns, l2_reg_linear, l2_reg_embedding, init_std, seed, task_types[0] if task_types else 'binary',
+                         device, gpus, flag, domain_column, len(task_names), linear_in_forward=False)
+        self.num_tasks, self.task_names = len(task_names), tuple(task_names)
+        inputs_dim = _field_count(dnn_feature_columns) * self.embedding.embedding_size + _dense_dim(dnn_feature_columns)
+        self.head = SharedBottomHead(inputs_dim, self.num_tasks, bottom_dnn_hidden_units, tower_dnn_hidden_units, init_std,
+                                     dnn_activation, dnn_dropout, dnn_use_bn)
+        self._finish()
+
+
+class PLE(_ScenarioModel):
+    """models/ple.py behind models/mtl_basemodel.py, one task per scenario, as MMOE: PLEHead returns each row's own task logit.
+    predict -> [n]."""
+    returns_column = False
+
+    def __init__(self, dnn_feature_columns, shared_expert_num=1, specific_expert_num=1, num_levels=2, expert_dnn_hidden_units=(256, 128),
+                 gate_dnn_hidden_units=(64,), tower_dnn_hidden_units=(64,), l2_reg_linear=0.00001, l2_reg_embedding=0.00001,
+                 l2_reg_dnn=0, init_std=0.0001, seed=1024, dnn_dropout=0, dnn_activation='relu', dnn_use_bn=False,
+                 task_types=('binary', 'binary'), task_names=('ctr', 'ctcvr'), device='cpu', gpus=None, domain_column=None, flag=None):
+        _check_tasks("PLE", flag, task_types, task_names, domain_column)
+        _refuse_options("PLEHead", l2_reg_dnn=(l2_reg_dnn, 0))
+        super().__init__([], dnn_feature_columns, l2_reg_linear, l2_reg_embedding, init_std, seed, task_types[0] if task_types else 'binary',
+                         device, gpus, flag, domain_column, len(task_names), linear_in_forward=False)
+        self.num_tasks, self.task_names = len(task_names), tuple(task_names)
+        inputs_dim = _field_count(dnn_feature_columns) * self.embedding.embedding_size + _dense_dim(dnn_feature_columns)
+        self.head = PLEHead(inputs_dim, self.num_tasks, shared_expert_num, specific_expert_num, num_levels, expert_dnn_hidden_units,
+                            gate_dnn_hidden_units, tower_dnn_hidden_units, init_std, dnn_activation, dnn_dropout, dnn_use_bn)
+        self._finish()
+
+
+class ESMM(HeadModel):
+    """models/esmm.py behind models/mtl_basemodel.py: ESMMHead returns the probabilities (p_ctr, p_ctr * p_cvr) of every row, and
+    a row's loss and prediction are taken on the column of its own task - the masked per-task loss sum (mtl_basemodel.py:268-269)
+    and predict's assembly (:376-378) - by RoutedPointLoss with the linear prediction kind, in one launch.  A row whose id is
+    neither of the two tasks' takes part in no loss and predicts 0, as in the reference.  Exactly two tasks, binary only, no
+    `flag` parameter (esmm.py:38-57).  predict -> [n].  dnn_dropout is ESMMHead's (the kernels' own masks)."""
+    returns_column = False
+    uses_domains = True
+
+    def __init__(self, dnn_feature_columns, tower_dnn_hidden_units=(256, 128), l2_reg_linear=0.00001, l2_reg_embedding=0.00001,
+                 l2_reg_dnn=0, init_std=0.0001, seed=1024, dnn_dropout=0, dnn_activation='relu', dnn_use_bn=False,
+                 task_types=('binary', 'binary'), task_names=('ctr', 'ctcvr'), device='cpu', gpus=None, domain_column=None):
+        if len(task_names) != 2:
+            raise ValueError("the length of task_names must be equal to 2")
+        if len(dnn_feature_columns) == 0:
+            raise ValueError("dnn_feature_columns is null!")
+        if len(task_types) != 2:
+            raise ValueError("num_tasks must be equal to the length of task_types")
+        for task_type in task_types:
+            if task_type != 'binary':
+                raise ValueError("task must be binary in ESMM, {} is illegal".format(task_type))
+        if domain_column is None:
+            raise ValueError("ESMM: domain_column names the column whose id picks a row's task")
+        super().__init__([], dnn_feature_columns, l2_reg_linear, l2_reg_embedding, init_std, seed, 'binary', device, gpus, None,
+                         domain_column, 2, linear_in_forward=False)
+        self.num_tasks, self.task_names = 2, tuple(task_names)
+        inputs_dim = _field_count(dnn_feature_columns) * self.embedding.embedding_size + _dense_dim(dnn_feature_columns)
+        self.head = ESMMHead(inputs_dim, tower_dnn_hidden_units, l2_reg_dnn, init_std, dnn_dropout, dnn_activation, dnn_use_bn)
+        self._routed = RoutedPointLoss("binary_crossentropy", "regression")
+        self._finish()
+
+    def compile(self, optimizer, loss=None, metrics=None):
+        super().compile(optimizer, loss, metrics)
+        self._routed = RoutedPointLoss(self.loss_func, "regression")      # (the head's outputs are probabilities already)
+
+    def _task_ids(self, X):
+        return self._domain_ids(X).long() - self.domain_id_offset
+
+    def _loss_and_pred(self, X, y=None):
+        return self._routed(self.head(self._dnn_input(X)), self._task_ids(X), y)

@@ -592,6 +592,7 @@ SIGNATURES = {
                                     _vp, _vp, _vp, _vp, C.c_int, _vp]),
     "satrans_point_loss_partials": (C.c_int64, [C.c_int]),
     "satrans_point_loss": (C.c_int, [_vp, C.c_int64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "satrans_point_loss_routed": (C.c_int, [_vp, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     "satrans_optim_flat": (C.c_int, [C.c_int, _vp, _vp, _vp, C.c_int64, C.c_float, C.c_float, C.c_float, _vp]),
     "satrans_adam_flat": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.POINTER(AdamHParams), _vp]),
     "satrans_adam_flat_sum": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.POINTER(AdamHParams), _vp, C.c_int64, _vp, _vp]),

@@ -1,7 +1,8 @@
-"""Generate tests/golden/models/{wdl,deepfm,dcn_vector,dcn_matrix,mmoe,star}.npz by running the REFERENCE's own model classes
-through their own compile() / fit() / predict() (CPU; build container only).
+"""Generate tests/golden/models/{wdl,deepfm,dcn_vector,dcn_matrix,mmoe,star}.npz and the ten of MORE_CASES by running the
+REFERENCE's own model classes through their own compile() / fit() / predict() (CPU; build container only).
 
     PYTHONDONTWRITEBYTECODE=1 python tools/gen_models_golden.py          # writes tests/golden/models/*.npz
+    PYTHONDONTWRITEBYTECODE=1 python tools/gen_models_golden.py esmm ple # only these cases
 
 The reference (read-only, never copied) is imported exactly as oracle/gen_golden.py imports it, with the stand-in packages of
 oracle/shims/ on sys.path.  deepctr's `DNN`, `combined_dnn_input`, `FM` and `CrossNet` are off the SATrans path and absent from the
@@ -12,7 +13,11 @@ Case shape: D = 16; columns dom (3 scenarios; ids start at 1 for mmoe and star, 
 (37), cate (4), one dense `price`; hidden units (16, 8) (mmoe: experts (16, 8), gates (8,), towers (8,)); 96 rows as three batches
 of 32, every batch holding at least two rows of every scenario (asserted); l2_reg_embedding = l2_reg_linear = 1e-5, Adam lr 1e-3,
 shuffle=False, 2 epochs: six Adam steps.  wdl, deepfm and dcn are built without `domain_column`, which would only add the
-reference's unused meta modules.  All parameters are overwritten with values of a visible size.  Recorded per case (arrays only):
+reference's unused meta modules.  The ten further cases (MORE_CASES) keep that shape with small case-specific sizes: xdeepfm CIN
+(8, 8); afm attention factor 4; autoint two interacting layers of two heads; pnn inner and 'mat' outer products; adasparse
+domain_emb_dim = D over `dom` (ids from 0); sharedbottom and ple towers (8,), ple gates (8,), ids from 1; esmm two scenarios,
+ids from 1, built without `flag` (its constructor has none).  Their layers come from the earlier generators too
+(gen_cin_golden.py, gen_fm_golden.py, gen_autoint_golden.py, gen_fibinet_golden.py, gen_pnn_golden.py, gen_adasparse_golden.py).  All parameters are overwritten with values of a visible size.  Recorded per case (arrays only):
 
   x/<name>, y                      the model input by column, the labels
   keys                             the reference's state_dict() key list, in order
@@ -48,12 +53,27 @@ import gen_fm_golden as FG  # noqa: E402  (StandInFM; imports the reference's de
 import gen_star_golden as SG  # noqa: E402  (TowerDNN, combined_dnn_input; imports the reference's star)
 import gen_esmm_golden as EG  # noqa: E402,F401  (imports the reference's wdl)
 import gen_mmoe_golden as MG  # noqa: E402,F401  (imports the reference's mmoe)
+import gen_cin_golden as CG  # noqa: E402  (StandInCIN; imports the reference's xdeepfm)
+import gen_autoint_golden as AG  # noqa: E402  (StandInInteractingLayer; imports the reference's autoint)
+import gen_fibinet_golden as BG  # noqa: E402  (StandInSENET, StandInBilinear; imports the reference's fibinet)
+import gen_pnn_golden as PG  # noqa: E402  (StandInInner, StandInOuter; imports the reference's pnn)
+import gen_adasparse_golden as SPG  # noqa: E402,F401  (imports the reference's adasparse)
 from deepctr_torch.inputs import DenseFeat, SparseFeat  # noqa: E402  (shim)
 import models.dcn as dcn  # noqa: E402  (the reference)
 import models.deepfm as deepfm  # noqa: E402
 import models.mmoe as mmoe  # noqa: E402
 import models.star as star  # noqa: E402
 import models.wdl as wdl  # noqa: E402
+import models.adasparse as adasparse  # noqa: E402
+import models.afm as afm  # noqa: E402
+import models.autoint as autoint  # noqa: E402
+import models.esmm as esmm  # noqa: E402
+import models.fibinet as fibinet  # noqa: E402
+import models.nfm as nfm  # noqa: E402
+import models.ple as ple  # noqa: E402
+import models.pnn as pnn  # noqa: E402
+import models.sharedbottom as sharedbottom  # noqa: E402
+import models.xdeepfm as xdeepfm  # noqa: E402
 
 for module in (wdl, deepfm, dcn, mmoe):
     module.DNN = DG.PlainDNN
@@ -62,10 +82,23 @@ deepfm.FM = FG.StandInFM
 dcn.CrossNet = DG.StandInCrossNet
 star.DNN = SG.TowerDNN
 star.combined_dnn_input = SG.combined_dnn_input
+for module in (xdeepfm, nfm, autoint, fibinet, pnn, sharedbottom, ple, esmm):
+    module.DNN = DG.PlainDNN
+for module in (xdeepfm, nfm, fibinet, pnn, adasparse, sharedbottom, ple, esmm):
+    module.combined_dnn_input = SG.combined_dnn_input
+xdeepfm.CIN = CG.StandInCIN
+nfm.BiInteractionPooling = FG.StandInBiPooling
+afm.AFMLayer, afm.FM = FG.StandInAFM, FG.StandInFM
+autoint.InteractingLayer = AG.StandInInteractingLayer
+fibinet.SENETLayer, fibinet.BilinearInteraction = BG.StandInSENET, BG.StandInBilinear
+pnn.InnerProductLayer, pnn.OutterProductLayer = PG.StandInInner, PG.StandInOuter
 
 D, ROWS, BATCH, S, UNITS, L2, LR, EPOCHS = 16, 96, 32, 3, (16, 8), 1e-5, 1e-3, 2
 VOCAB = {"dom": S, "user": 50, "item": 37, "cate": 4}
 CASES = ("wdl", "deepfm", "dcn_vector", "dcn_matrix", "mmoe", "star")
+MORE_CASES = ("xdeepfm", "nfm", "afm", "autoint", "fibinet", "pnn", "adasparse", "sharedbottom", "ple", "esmm")
+MULTI_TASK = ("mmoe", "sharedbottom", "ple", "esmm")
+FROM_ONE = MULTI_TASK + ("star",)                      # scenario ids start at 1
 
 
 def build(name, cols, offset):
@@ -82,8 +115,38 @@ def build(name, cols, offset):
         return mmoe.MMOE, dict(dnn_feature_columns=cols, expert_dnn_hidden_units=UNITS, gate_dnn_hidden_units=(8,),
                                tower_dnn_hidden_units=(8,), l2_reg_linear=L2, task_types=["binary"] * S,
                                task_names=["ctr%d" % i for i in range(S)], domain_column="dom", **common)
+    both = dict(linear_feature_columns=cols, dnn_feature_columns=cols)
+    tasks = dict(task_types=["binary"] * scenarios(name), task_names=["ctr%d" % i for i in range(scenarios(name))], domain_column="dom")
+    if name == "xdeepfm":
+        return xdeepfm.xDeepFM, dict(dnn_hidden_units=UNITS, cin_layer_size=(8, 8), l2_reg_linear=L2, **both, **common)
+    if name == "nfm":
+        return nfm.NFM, dict(dnn_hidden_units=UNITS, l2_reg_linear=L2, **both, **common)
+    if name == "afm":
+        return afm.AFM, dict(attention_factor=4, l2_reg_linear=L2, **both, **common)
+    if name == "autoint":
+        return autoint.AutoInt, dict(att_layer_num=2, att_head_num=2, dnn_hidden_units=UNITS, **both, **common)
+    if name == "fibinet":
+        return fibinet.FiBiNET, dict(dnn_hidden_units=UNITS, l2_reg_linear=L2, **both, **common)
+    if name == "pnn":
+        return pnn.PNN, dict(dnn_feature_columns=cols, dnn_hidden_units=UNITS, use_inner=True, use_outter=True, **common)
+    if name == "adasparse":
+        return adasparse.AdaSparse, dict(dnn_hidden_units=UNITS, l2_reg_linear=L2, domain_column="dom", num_domains=S, domain_emb_dim=D,
+                                         **both, **common)
+    if name == "sharedbottom":
+        return sharedbottom.SharedBottom, dict(dnn_feature_columns=cols, bottom_dnn_hidden_units=UNITS, tower_dnn_hidden_units=(8,),
+                                               l2_reg_linear=L2, **tasks, **common)
+    if name == "ple":
+        return ple.PLE, dict(dnn_feature_columns=cols, expert_dnn_hidden_units=UNITS, gate_dnn_hidden_units=(8,),
+                             tower_dnn_hidden_units=(8,), l2_reg_linear=L2, **tasks, **common)
+    if name == "esmm":
+        common.pop("flag")
+        return esmm.ESMM, dict(dnn_feature_columns=cols, tower_dnn_hidden_units=UNITS, l2_reg_linear=L2, **tasks, **common)
     return star.Star_Net, dict(linear_feature_columns=cols, dnn_feature_columns=cols, domain_column="dom", num_domains=S,
                                domain_id_as_feature=True, dnn_hidden_units=UNITS, use_domain_dnn=True, use_domain_bn=True, **common)
+
+
+def scenarios(name):
+    return 2 if name == "esmm" else S
 
 
 def visible(rng, key, shape):
@@ -96,6 +159,8 @@ def visible(rng, key, shape):
         return 0.3 * rng.randn(*shape)
     if key.endswith("shared_bn_weight") or (key.startswith("bns.") and key.endswith("weight")):
         return 1.0 + 0.2 * rng.randn(*shape)
+    if key.startswith("cin.conv1ds.") and len(shape) == 3:      # [out, in, 1]
+        return rng.randn(*shape) * shape[1] ** -0.5
     if len(shape) >= 2 and "bias" not in key:
         return rng.randn(*shape) * shape[-1] ** -0.5
     return 0.3 * rng.randn(*shape)
@@ -108,7 +173,8 @@ def quiet(fn, *args, **kwargs):
 
 def run_case(name, outdir):
     rng = np.random.RandomState(sum(map(ord, name)) + 5)
-    offset = 1 if name in ("mmoe", "star") else 0
+    offset = 1 if name in FROM_ONE else 0
+    S = scenarios(name)
     vocab = dict(VOCAB, dom=S + offset)
     cols = [SparseFeat(k, v, embedding_dim=D) for k, v in vocab.items()] + [DenseFeat("price", 1)]
     x = {}
@@ -122,7 +188,7 @@ def run_case(name, outdir):
     x["price"] = rng.rand(ROWS).astype(np.float32)
     y = (rng.rand(ROWS) < 0.35).astype(np.float32)
     cls, kwargs = build(name, cols, offset)
-    loss_arg = ["binary_crossentropy"] * S if name == "mmoe" else "binary_crossentropy"
+    loss_arg = ["binary_crossentropy"] * S if name in MULTI_TASK else "binary_crossentropy"
 
     def fresh(init=None):
         model = cls(**kwargs)
@@ -168,7 +234,7 @@ def run_case(name, outdir):
     X0 = torch.from_numpy(np.stack([x[k][:BATCH].astype(np.float32) for k in model.feature_index], axis=1))
     y0 = torch.from_numpy(y[:BATCH])
     y_pred = model(X0)
-    if name == "mmoe":
+    if name in MULTI_TASK:
         ids = torch.from_numpy(dom[:BATCH])
         loss0 = sum(F.binary_cross_entropy(y_pred[:, i][ids == i + offset], y0[ids == i + offset], reduction='sum') for i in range(S))
     else:
@@ -189,5 +255,5 @@ def run_case(name, outdir):
 
 if __name__ == "__main__":
     outdir = os.path.join(ROOT, "tests", "golden", "models")
-    for case in (sys.argv[1:] or list(CASES)):
+    for case in (sys.argv[1:] or list(CASES + MORE_CASES)):
         run_case(case, outdir)
